@@ -24,8 +24,20 @@ The timed region is bracketed by barrier + synchronize and the max over ranks
 is used.
 
 Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (timed
-with hipEvents on the block's stream over the timed region) and the oracle's
-CPU timing on a bounded sample (rank 0, N=1).
+with hipEvents on the block's stream over the timed region).
+
+A plain run does only what the headline figure needs: set up, W warm-up steps,
+the K timed steps, the line.  ``--full`` adds everything that takes runs of its
+own: the oracle's CPU timing on a bounded sample (rank 0, N=1), config 2's linear
+filter (``linear``), config 3 (``net``) with its roofline and CPU baseline, and
+for N > 1 the replica upper bound and the sharded-output check; the ``--*-check``
+/ ``--cpu-baseline`` switches select among them under ``--full``.
+
+``--dump-outputs DIR`` writes the output of the last timed step (what a caller of
+the timed path receives) as ``DIR/y.npy`` (``DIR/y_rank<r>.npy`` for N > 1),
+float32: the whole array when it is small, otherwise a fixed, seeded sample of
+its elements in flat (row-major) order.  Inputs and weights are seeded, so two
+runs with the same arguments see identical inputs.
 """
 from __future__ import annotations
 
@@ -208,7 +220,14 @@ def parse(argv=None):
     ap.add_argument("--nlat", type=int, default=721)
     ap.add_argument("--nlon", type=int, default=1440)
     ap.add_argument("--lmax", type=int, default=360)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="time the oracle on CPU (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure (CPU baselines, the "
+                         "linear filter, the network line, replica bound and sharded check)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's output as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample when the array is large)")
+    ap.add_argument("--cpu-baseline", type=int, default=1,
+                    help="--full: time the oracle on CPU (rank 0, N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads (0: the physical cores this job may use, see host_cores)")
     ap.add_argument("--cpu-reps", type=int, default=3, help="timed oracle reps after 1 warm-up (median)")
@@ -230,15 +249,16 @@ def parse(argv=None):
                     help="--workload net, latband: shard every block, or replicate the inner "
                          "(h, w) blocks on every rank after one all-gather (SURVEY 8(e))")
     ap.add_argument("--replicas-check", type=int, default=1,
-                    help="latband, N>1: also time the replica mode (comm-free upper bound)")
+                    help="--full, latband, N>1: also time the replica mode (comm-free upper "
+                         "bound)")
     ap.add_argument("--linear-check", type=int, default=1,
-                    help="N=1, non-linear headline: also time config 2's linear filter (the "
+                    help="--full, N=1, non-linear headline: also time config 2's linear filter (the "
                          "per-mode weight stream) and print it as the line's 'linear' object")
     ap.add_argument("--net-check", type=int, default=1,
-                    help="N=1 block headline: also time config 3 (the 12-block filmed net, "
+                    help="--full, N=1 block headline: also time config 3 (the 12-block filmed net, "
                          "one 6 h step) and print it as the line's 'net' object")
     ap.add_argument("--band-check", type=int, default=1,
-                    help="latband, N>1: after the timed region compare field 0's sharded "
+                    help="--full, latband, N>1: after the timed region compare field 0's sharded "
                          "output with the whole-field block on rank 0 (max-abs in the line)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group check only (gloo, no GPU): ranks report in")
@@ -505,8 +525,10 @@ def run_net(args, rank, world, dev, dist, backend):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
     assert torch.isfinite(y).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
     roof = None
-    if rank == 0 and not band:
+    if rank == 0 and not band and args.full:
         # roofline of the step's dominant kernel: one more (untimed, eager) step with
         # the stage profiler on (the graph replay above cannot be split into kernels)
         from msfno_amd import _native as N
@@ -587,6 +609,7 @@ def net_line(args, dev):
     na = copy.copy(args)
     na.workload = "net"
     na.graph = -1
+    na.dump_outputs = None  # the dump is the headline path's output
     torch.cuda.empty_cache()
     line = run_net(na, 0, 1, dev, False, "nccl")
     if args.cpu_baseline:
@@ -672,6 +695,30 @@ def _max_over_ranks(v, dist, dev, backend):
     t = torch.tensor([v], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
     torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     return t.item()
+
+
+# --dump-outputs: float32 values written per run, over all ranks (32 MiB of the 64 MB
+# a dump may take)
+DUMP_MAX_VALUES = 8 << 20
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(dirname, y, rank, world):
+    """The last timed step's output as DIR/y.npy (DIR/y_rank<r>.npy for N > 1), float32,
+    flattened row-major.  An output of more than DUMP_MAX_VALUES / N values is sampled:
+    the flat indices are drawn once from a host generator with a fixed seed (with
+    replacement, in drawing order), so the same arguments pick the same elements in
+    every run and every build."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    flat = y.detach().reshape(-1)
+    limit = DUMP_MAX_VALUES // world
+    if flat.numel() > limit:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(flat.numel(), (limit,), generator=g)
+        flat = flat[idx.to(flat.device)]
+    name = "y.npy" if world == 1 else f"y_rank{rank}.npy"
+    np.save(os.path.join(dirname, name), flat.float().cpu().numpy())
 
 
 def timed(step, args, dist, dev, backend):
@@ -933,13 +980,16 @@ def main():
     if args.stages:
         print_stages(stages, args, B_launch, C, rows, mset, tag=f"rank{rank} ")
     assert torch.isfinite(y).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
 
+    # everything below the headline figure takes runs of its own: --full only
     check = None
-    if band and dist and args.band_check:
+    if args.full and band and dist and args.band_check:
         check = band_check(shard, blk, y, gamma, beta, args, rank, world, dev, backend)
 
     replicas = None
-    if band and dist and args.replicas_check:
+    if args.full and band and dist and args.replicas_check:
         # the comm-free upper bound: every rank runs its own batch fields whole
         del x, shard
         torch.cuda.empty_cache()
@@ -972,16 +1022,18 @@ def main():
                          "m_per_rank": [q["m_count"] for q in per_rank]}
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         del blk
         torch.cuda.empty_cache()
         cpu = cpu_baseline(args, p, cfg)
 
     linear = None
-    if world == 1 and args.linear_check and args.filter == "non-linear" and not band:
+    if args.full and world == 1 and args.linear_check and args.filter == "non-linear" \
+            and not band:
         linear = linear_line(args, dev)
     net = None
-    if world == 1 and args.net_check and not band and (args.nlat, args.nlon) == (721, 1440):
+    if args.full and world == 1 and args.net_check and not band \
+            and (args.nlat, args.nlon) == (721, 1440):
         net = net_line(args, dev)
 
     if rank == 0:

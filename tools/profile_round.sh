@@ -4,7 +4,7 @@
 #      block line (kt_linear) and the 12-block network line (kt_net)
 #   2. separate FETCH_SIZE and WRITE_SIZE PMC passes over the same three workloads
 #      (MI355X_MICROARCH.md: one TCC counter group per pass)
-#   3. the plain bench line (all objects, CPU baseline) with per-stage timings
+#   3. the full bench line (--full: all objects, CPU baseline) with per-stage timings
 # usage: bash tools/profile_round.sh gpurun_out/<tag>;  then on the build host
 #        python tools/rocpd_summary.py gpurun_out/<tag> profiles/<tag>
 OUT=${1:-gpurun_out/prof}
@@ -20,5 +20,5 @@ for w in "" _linear _net; do
       python3 bench.py --steps 2 --warmup 1 $ONE ${W[$w]} > $OUT/bench_$p$w.json 2> $OUT/bench_$p$w.err || exit $?
   done
 done
-timeout -k 10 400 python3 bench.py --stages > $OUT/bench.json 2> $OUT/bench_stages.txt && \
+timeout -k 10 400 python3 bench.py --full --stages > $OUT/bench.json 2> $OUT/bench_stages.txt && \
 cat $OUT/bench.json
