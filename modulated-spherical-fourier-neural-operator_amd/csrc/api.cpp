@@ -295,9 +295,7 @@ int side_ctx(std::shared_ptr<SideCtx>* out, hipStream_t caller) {
 // ---------------------------------------------------------------------------
 
 // Legendre GEMM tiles (descriptor layout and launch must agree)
-static GemmTile leg_tile(int inverse) {
-  return inverse ? role_tile(ROLE_LEGI, TILE_128x128) : role_tile(ROLE_LEG, TILE_128x64);
-}
+static GemmTile leg_tile(int inverse) { return inverse ? TILE_128x128 : TILE_128x64; }
 
 // the per-(m, parity) Legendre problems of a plan for R rows, in launch order:
 // forward A = Xt slab (R x K), B = table, C = S (ld ldT); inverse A = S (ld ldT),
@@ -312,10 +310,8 @@ static void leg_problems(const msfno_sht_plan_s* p, int R, int64_t ldT,
     const int64_t slab = (int64_t)p->slab[m] * R * p->ldk;
     const int lpe = L.Lpe[m], lpo = L.Lp[m] - L.Lpe[m];
     const int le = (L.L[m] + 1) / 2, lo = L.L[m] / 2;
-    const int flags = (!p->inverse && m > 0) ? 1 : 0;  // m = 0 is normalised by dc_fixup
     GemmDesc g{};
     g.M = R;
-    g.flags = flags;
     if (p->band_world) {
       // band plan: A (forward) / C (inverse) is the exchange buffer [p][slab][R][2W],
       // its K / N index the exchange columns (segmented in the launch, legendre_*)
@@ -438,25 +434,7 @@ int ensure_desc(msfno_sht_plan_s* p, int R, int other_ld, int64_t ldT, hipStream
   gemm_tile_dims(leg_tile(p->inverse), &bm, &bn);
   std::vector<GemmDesc> d;
   int tiles = 0;
-  // MSFNO_LEG_COMPACT=1 (diagnostic timing only, wrong results): the S operand of every
-  // problem as its own compact [R][N] block instead of columns of the [R][ldT] rows
-  static const bool compact = [] {
-    const char* e = getenv("MSFNO_LEG_COMPACT");
-    return e && e[0] == '1';
-  }();
-  int64_t coff = 0;
   leg_problems(p, R, ldT, [&](GemmDesc g) {
-    if (compact && !p->band_world) {
-      if (!p->inverse) {
-        g.ldc = (int)round_up(g.N, 4);
-        g.offC = coff;
-        coff += (int64_t)R * g.ldc;
-      } else {
-        g.lda = (int)round_up(std::max(g.K, 1), 4);
-        g.offA = coff;
-        coff += (int64_t)R * g.lda;
-      }
-    }
     g.tiles_m = (int)cdiv(g.M, bm);
     g.tiles_n = (int)cdiv(g.N, bn);
     if (g.tiles_m * g.tiles_n == 0) return;
@@ -527,7 +505,7 @@ static int ensure_desc3(msfno_sht_plan_s* p, int R, int64_t ldT, hipStream_t s) 
   int64_t img = 0, sc = 0;
   leg_problems(p, R, ldT, [&](GemmDesc g) {
     g.tiles_m = (int)cdiv(g.M, X3D_BM);
-    g.tiles_n = res ? 1 : (int)cdiv(g.N, x3d_bn(p->inverse));
+    g.tiles_n = res ? 1 : (int)cdiv(g.N, X3D_BN);
     // every problem gets its image, also K = 0 ones (written as zeros)
     g.offBx = img;
     g.offBs = sc;
@@ -650,17 +628,6 @@ int legendre_fwd_x3f(msfno_sht_plan_s* f, const unsigned short* Xp, const float*
                       f->ndesc3f, f->desc3f_tiles, s, segw, segs);
 }
 
-// spectral MLP: Gauss 3M complex GEMM by default (MSFNO_SPEC_4M=1: the real-ified
-// 4-multiplication GEMM, kept as an A/B switch); MSFNO_C3M_TILE picks its tile
-bool use_c3m() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MSFNO_SPEC_4M");
-    mode = (e && e[0] == '1') ? 0 : 1;
-  }
-  return mode == 1;
-}
-
 // spectral MLP on the x6 engine (real-ified 4-multiplication GEMM on the bf16
 // matrix cores, fp32-accurate split) whenever the dense GEMMs use it;
 // MSFNO_SPEC_X6=0 keeps the fp32 3M kernel for A/B
@@ -670,27 +637,6 @@ bool spec_use_x6() {
     return gemm_use_x6() && !(e && e[0] == '0');
   }();
   return on;
-}
-
-int c3m_tile() {
-  static int t = -1;
-  if (t < 0) {
-    const char* e = getenv("MSFNO_C3M_TILE");
-    t = e ? atoi(e) : 1;  // 64x128 measured best (in-block A/B)
-  }
-  return t;
-}
-
-// MSFNO_FFT_TILE=1 selects the fused FFT+transpose tile kernels instead of the
-// row FFT + separate transpose kernels (measured slower on MI355X at 721x1440:
-// DESIGN.md §5); kept as an A/B switch.
-bool use_fft_tile(const msfno_sht_plan_s* p) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("MSFNO_FFT_TILE");
-    mode = (e && e[0] == '1') ? 1 : 0;
-  }
-  return mode == 1 && !p->sym && fft_tile_supported(p->fft);  // tile kernels: general layout
 }
 
 // Xn (BC, nlat, mmax) -> the plan's slab layout (hemispheres folded when symmetric)
@@ -707,9 +653,8 @@ int transpose_inv_plan(const msfno_sht_plan_s* p, const float* Yt, float2* Yn, i
   return launch_transpose_inv(Yt, Yn, B, C, p->nlat, p->mmax, p->spec.mact, p->ldk, s);
 }
 
-int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStream_t s,
-                 const float* rowscale, int C) {
-  if (leg_x3_enabled() && !rowscale) {
+int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStream_t s) {
+  if (leg_x3_enabled()) {
     MSFNO_TRY(ensure_desc3(f, R, f->spec.ldT, s));
     GemmEpi e;
     if (f->band_world) {
@@ -717,12 +662,10 @@ int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStrea
       e.segA_stride = (int64_t)f->nslab * R * 2 * f->band_W;
     }
     return legendre_x3(Xt, f->tab3, f->tab3s, S, f->d_desc3, f->d_tile3, f->ndesc3,
-                       f->desc3_tiles, x3d_bn(0), e, s);
+                       f->desc3_tiles, e, s);
   }
   MSFNO_TRY(ensure_desc(f, R, 0, f->spec.ldT, s));
   GemmEpi e;
-  e.rowscale = rowscale;
-  e.rs_C = C;
   if (f->band_world) {  // Xt is the phase-0 receive buffer: one block per source rank
     e.segA_w = f->band_seg();
     e.segA_stride = (int64_t)f->nslab * R * 2 * f->band_W;
@@ -743,7 +686,7 @@ int legendre_inv(msfno_sht_plan_s* g, const float* S, float* Yt, int R, hipStrea
       return legendre_x3r(S, g->tab3, g->tab3s, Yt, g->d_desc3, g->d_tile3, g->ndesc3,
                           g->desc3_tiles, e, s);
     return legendre_x3(S, g->tab3, g->tab3s, Yt, g->d_desc3, g->d_tile3, g->ndesc3,
-                       g->desc3_tiles, x3d_bn(1), e, s);
+                       g->desc3_tiles, e, s);
   }
   MSFNO_TRY(ensure_desc(g, R, 0, g->spec.ldT, s));
   GemmEpi e;
@@ -874,9 +817,10 @@ bool spec_use_x3h() {
 // bf16x3 planes with a row stride padded to 8 on the x6 engine
 int64_t spec_hidden_floats(int B, int64_t Hs, const SpecLayout& L) {
   if (!spec_use_x6()) return (int64_t)B * 2 * Hs * L.ldT;
-  const int64_t planes = spec_use_3m() ? 9 : 6;  // 3M: re, im, re+im; 4M: re/im rows
+  // 4M: re / im rows as 3 planes each, row stride padded to 8; 3M: the tiled layout of
+  // re, im, re + im (never smaller than the 4M form)
   return std::max<int64_t>({(int64_t)B * 2 * Hs * L.ldT,
-                            cdiv((int64_t)B * planes * Hs * round_up(L.Tp, 8) * 2, 4),
+                            cdiv((int64_t)B * 6 * Hs * round_up(L.Tp, 8) * 2, 4),
                             cdiv((int64_t)B * x6c_tiled_elems((int)Hs, (int)L.Tp) * 2, 4)});
 }
 
@@ -944,10 +888,10 @@ int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s*
     const int64_t Hs = d->spec_hidden;
     prof(ST_SPEC_PREP, s);
     const bool x6 = spec_use_x6() && b.dw.spec[0];
-    const bool c3m = !x6 && use_c3m();
+    const bool c3m = !x6;  // fp32 engine: Gauss 3M complex GEMM (cgemm.hip)
     if (x6 && spec_use_3m() && C <= Hs) {
       // Gauss 3M complex GEMMs (gemm_x6c.hip): weights Wr, Wi, Wr+Wi of all layers in
-      // one launch; layer 0's input split into 3M planes in Sc (free until layer 1)
+      // one launch; layer 0 splits its fp32 input while staging it
       SpecWeightsX6p sw{};
       sw.nlayers = nl + 1;
       for (int l = 0; l <= nl; ++l) {
@@ -985,43 +929,16 @@ int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s*
       }
       if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_3m(sw, s));
       const int ldTx = (int)round_up(L.Tp, 8);
-      unsigned short* cur = reinterpret_cast<unsigned short*>(b.Sc);
-      // layer 0 stages S fp32 and splits it in-kernel (no split3m pass, 0.1 ms less
-      // per block at config 2); MSFNO_SPEC_L0F32=0 restores the separate split3m
-      static const bool l0f32 = [] {
-        const char* e = getenv("MSFNO_SPEC_L0F32");
-        return !(e && e[0] == '0');
-      }();
-      const bool f32b = l0f32 && nl >= 1 && L.ldT % 4 == 0;
-      // hidden activations in the tiled layout (gemm_x6c.hip; spectral MLP 8 % faster
-      // at config 2); MSFNO_X6C_TILED=0: row layout [b][mat][plane][c][ld]
-      static const bool tiled = [] {
-        const char* e = getenv("MSFNO_X6C_TILED");
-        return !(e && e[0] == '0');
-      }();
-      if (f32b && tiled) {
-        for (int l = 0; l <= nl; ++l) {
-          prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
-          unsigned short* out = l == nl ? nullptr
-                                        : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
-          if (l == 0)
-            MSFNO_TRY(gemm_x6c_f32b(sw.out[0], sw.co[0], sw.ci[0], b.Sa, (int)L.ldT, (int)L.Tp, out,
-                                    ldTx, nullptr, 0, true, B, s, true));
-          else
-            MSFNO_TRY(gemm_x6c(sw.out[l], sw.co[l], sw.ci[l], cur, (int)L.Tp, ldTx, out,
-                               l == nl ? b.Sa : nullptr, (int)L.ldT, l < nl, B, s, l == nl ? 1 : 3));
-          cur = out;
-        }
-        return MSFNO_OK;
-      }
-      if (!f32b) MSFNO_TRY(launch_split3m(b.Sa, cur, B, (int)C, (int)L.Tp, (int)L.ldT, ldTx, s));
+      unsigned short* cur = nullptr;
+      // layer 0 stages S fp32 and splits it in-kernel; hidden activations travel in the
+      // tiled layout (gemm_x6c.hip)
       for (int l = 0; l <= nl; ++l) {
         prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
         unsigned short* out = l == nl ? nullptr
                                       : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
-        if (l == 0 && f32b)
+        if (l == 0)
           MSFNO_TRY(gemm_x6c_f32b(sw.out[0], sw.co[0], sw.ci[0], b.Sa, (int)L.ldT, (int)L.Tp, out,
-                                  ldTx, nullptr, 0, true, B, s));
+                                  ldTx, true, B, s));
         else
           MSFNO_TRY(gemm_x6c(sw.out[l], sw.co[l], sw.ci[l], cur, (int)L.Tp, ldTx, out,
                              l == nl ? b.Sa : nullptr, (int)L.ldT, l < nl, B, s));
@@ -1090,7 +1007,7 @@ int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s*
           MSFNO_TRY(gemm_x6p(b.Wexp[l], out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci, (int)ldTx, ldc, 0,
                              3 * 2LL * ci * ldTx, sC, B, e, b.dw.spec[l], b.dw.spec_b[l], s));
         } else if (l == 0) {
-          MSFNO_TRY(gemm_dense(ROLE_SPEC, TILE_128x128, b.Wexp[l], in, out, 2 * co, (int)L.Tp,
+          MSFNO_TRY(gemm_dense(TILE_128x128, b.Wexp[l], in, out, 2 * co, (int)L.Tp,
                                2 * ci, 2 * ci, (int)L.ldT, ldc, 0, 2LL * ci * L.ldT, sC, B, e,
                                b.dw.spec[l], b.dw.spec_b[l], s));
         } else {
@@ -1099,20 +1016,11 @@ int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s*
           MSFNO_TRY(gemm_x6p(b.Wexp[l], out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci, (int)ldTx, ldc, 0,
                              3 * 2LL * ci * ldTx, sC, B, e, b.dw.spec[l], b.dw.spec_b[l], s));
         }
-      } else if (c3m) {
+      } else {
         // Gauss 3-multiplication complex GEMM (cgemm.hip), ComplexReLU(real) fused
         MSFNO_TRY(gemm_c3m(b.Wexp[l], b.Wexp[l] + (int64_t)ci * co, in, out, co, ci, (int)L.Tp,
                            (int)L.ldT, (int)L.ldT, 2LL * ci * L.ldT, 2LL * co * L.ldT, B, l < nl,
-                           c3m_tile(), s));
-      } else {
-        GemmEpi e;
-        if (l < nl) {  // ComplexReLU(mode="real") on the real rows of each batch block
-          e.relu_period = 2 * co;
-          e.relu_rows = co;
-        }
-        MSFNO_TRY(gemm_uniform(role_tile(ROLE_SPEC, TILE_128x128), b.Wexp[l], in, out, 2 * co,
-                               (int)L.Tp, 2 * ci, 2 * ci, (int)L.ldT, (int)L.ldT, 0,
-                               2LL * ci * L.ldT, 2LL * co * L.ldT, B, e, s));
+                           s));
       }
       in = out;
     }
@@ -1142,45 +1050,29 @@ int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_
   const int64_t C = d->C, BC = (int64_t)B * C, R = 2 * BC;
   prof(ST_FFT_FWD, s);
   const float scale = (float)(2.0 * M_PI / f->nlon);
-  if (use_fft_tile(f)) {
-    // fused FFT + transpose; norm0 applied afterwards (m = 0 fix-up + GEMM row scale)
-    MSFNO_TRY(launch_fft_r2c_tile(f->fft, x, b.Xt, norm0 ? b.rs0 : nullptr, B, (int)C, f->nlat,
-                                  f->mmax, f->ldk, scale, s));
-    if (norm0) {
-      prof(ST_NORM0, s);
-      MSFNO_TRY(launch_chan_affine(b.rs0, f->nlat, f->nlon, f->nlon, B, (int)C, d->norm0_w,
-                                   d->norm0_b, d->norm_eps, nullptr, nullptr, 0.f, b.sc0, b.sh0,
-                                   s, b.xs));
-      if (after_norm0) MSFNO_TRY(after_norm0());
-      MSFNO_TRY(launch_dc_fixup(b.Xt, B, (int)C, f->nlat, f->ldk, b.sc0, b.sh0, s));
-    }
+  MSFNO_TRY(launch_fft_r2c_rows(f->fft, x, b.Xn, norm0 ? b.rs0 : nullptr, BC * f->nlat, f->mmax,
+                                scale, s, xplanes));
+  if (after_fft) MSFNO_TRY(after_fft());
+  if (norm0) {
+    prof(ST_NORM0, s);
+    MSFNO_TRY(launch_chan_affine(b.rs0, f->nlat, f->nlon, f->nlon, B, (int)C, d->norm0_w,
+                                 d->norm0_b, d->norm_eps, nullptr, nullptr, 0.f, b.sc0, b.sh0,
+                                 s, b.xs, b.lsig));
+    if (after_norm0) MSFNO_TRY(after_norm0());
+  }
+  prof(ST_TRANSPOSE_FWD, s);
+  if (norm0 && b.lsig && b.isr && x3f_usable(f)) {
+    // slab as x3h fp16 pairs in the Xt buffer (the fp32 bytes)
+    unsigned short* Xp = reinterpret_cast<unsigned short*>(b.Xt);
+    MSFNO_TRY(launch_transpose_fwd_sym_h(b.Xn, Xp, B, (int)C, f->geom(), f->mmax, b.sc0, b.sh0,
+                                         b.lsig, b.isr, s));
     prof(ST_LEG_FWD, s);
-    MSFNO_TRY(legendre_fwd(f, b.Xt, b.Sa, (int)R, s, norm0 ? b.sc0 : nullptr, (int)C));
+    MSFNO_TRY(legendre_fwd_x3f(f, Xp, b.isr, b.Sa, (int)R, s));
   } else {
-    MSFNO_TRY(launch_fft_r2c_rows(f->fft, x, b.Xn, norm0 ? b.rs0 : nullptr, BC * f->nlat, f->mmax,
-                                  scale, s, xplanes));
-    if (after_fft) MSFNO_TRY(after_fft());
-    if (norm0) {
-      prof(ST_NORM0, s);
-      MSFNO_TRY(launch_chan_affine(b.rs0, f->nlat, f->nlon, f->nlon, B, (int)C, d->norm0_w,
-                                   d->norm0_b, d->norm_eps, nullptr, nullptr, 0.f, b.sc0, b.sh0,
-                                   s, b.xs, b.lsig));
-      if (after_norm0) MSFNO_TRY(after_norm0());
-    }
-    prof(ST_TRANSPOSE_FWD, s);
-    if (norm0 && b.lsig && b.isr && x3f_usable(f)) {
-      // slab as x3h fp16 pairs in the Xt buffer (the fp32 bytes)
-      unsigned short* Xp = reinterpret_cast<unsigned short*>(b.Xt);
-      MSFNO_TRY(launch_transpose_fwd_sym_h(b.Xn, Xp, B, (int)C, f->geom(), f->mmax, b.sc0, b.sh0,
-                                           b.lsig, b.isr, s));
-      prof(ST_LEG_FWD, s);
-      MSFNO_TRY(legendre_fwd_x3f(f, Xp, b.isr, b.Sa, (int)R, s));
-    } else {
-      MSFNO_TRY(transpose_fwd_plan(f, b.Xn, b.Xt, B, (int)C, norm0 ? b.sc0 : nullptr,
-                                   norm0 ? b.sh0 : nullptr, s));
-      prof(ST_LEG_FWD, s);
-      MSFNO_TRY(legendre_fwd(f, b.Xt, b.Sa, (int)R, s));
-    }
+    MSFNO_TRY(transpose_fwd_plan(f, b.Xn, b.Xt, B, (int)C, norm0 ? b.sc0 : nullptr,
+                                 norm0 ? b.sh0 : nullptr, s));
+    prof(ST_LEG_FWD, s);
+    MSFNO_TRY(legendre_fwd(f, b.Xt, b.Sa, (int)R, s));
   }
   if (after_leg) MSFNO_TRY(after_leg());
   MSFNO_TRY(run_filter(d, f, g, b, B, s));
@@ -1191,16 +1083,11 @@ int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_
   return MSFNO_OK;
 }
 
-// Yt -> spatial rows (fused transpose + irfft when enabled); out = act(addsrc + irfft)
+// Yt -> spatial rows; out = act(addsrc + irfft)
 int run_inverse_fft(msfno_sht_plan_s* g, const BlockBufs& b, int B, int C, float* out,
                            const float* addsrc, float2* rowstats, int act, hipStream_t s,
                            unsigned short* planes = nullptr) {
   const int64_t BC = (int64_t)B * C;
-  if (use_fft_tile(g) && addsrc == nullptr) {
-    prof(ST_FFT_INV, s);
-    return launch_fft_c2r_tile(g->fft, b.Yt, out, rowstats, B, C, g->nlat, g->mmax,
-                               g->spec.mact, g->ldk, act, s);
-  }
   prof(ST_TRANSPOSE_INV, s);
   MSFNO_TRY(transpose_inv_plan(g, b.Yt, b.Yn, B, C, s));
   prof(ST_FFT_INV, s);
@@ -1335,37 +1222,6 @@ int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const
   const int64_t ldh = planes ? round_up(P, 8) : P;
   unsigned short* hx = planes ? reinterpret_cast<unsigned short*>(h) : nullptr;
   prof(ST_FC1, s);
-  const int64_t chunk = mlp_chunk(P);
-  if (planes && x1p && chunk > 0 && chunk < P) {
-    // pixel chunks: fc1 writes a chunk of h (planes) that fc2 reads back while it is
-    // still in the Infinity Cache; both weight images are split once
-    MSFNO_TRY(gemm_x6p_split_a(W1f, (int)Hd, (int)C, (int)C, Hd * C, B, dw.fc1, dw.fc1_b, s));
-    MSFNO_TRY(gemm_x6p_split_a(d->fc2_w, (int)C, (int)Hd, (int)Hd, 0, 1, dw.fc2, dw.fc2_b, s));
-    const int64_t ldc = round_up(chunk, 8);
-    for (int64_t p0 = 0; p0 < P; p0 += chunk) {
-      const int pc = (int)std::min<int64_t>(chunk, P - p0);
-      GemmEpi e1;
-      e1.bias = b1f;
-      e1.sBias = Hd;
-      e1.act = 1;
-      e1.a_planes = static_cast<const unsigned short*>(dw.fc1);
-      e1.b_planes = x1p + p0;
-      e1.b_plane_stride = C * P;
-      e1.c_planes = hx;
-      e1.c_plane_stride = Hd * ldc;
-      MSFNO_TRY(gemm_x6p(W1f, h, (int)Hd, pc, (int)C, (int)C, (int)P, (int)ldc, Hd * C, 3 * C * P,
-                         3 * Hd * ldc, B, e1, dw.fc1, dw.fc1_b, s));
-      GemmEpi e2;
-      e2.bias = d->fc2_b;
-      if (resid) { e2.addend = resid + p0; e2.sD = C * P; e2.ldd = (int)P; }
-      e2.a_planes = static_cast<const unsigned short*>(dw.fc2);
-      e2.b_planes = hx;
-      e2.b_plane_stride = Hd * ldc;
-      MSFNO_TRY(gemm_x6p(d->fc2_w, out + p0, (int)C, pc, (int)Hd, (int)Hd, (int)ldc, (int)P, 0,
-                         3 * Hd * ldc, C * P, B, e2, dw.fc2, dw.fc2_b, s));
-    }
-    return MSFNO_OK;
-  }
   GemmEpi e1;
   e1.bias = b1f;
   e1.sBias = Hd;
@@ -1378,7 +1234,7 @@ int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const
     MSFNO_TRY(gemm_x6p(W1f, h, (int)Hd, (int)P, (int)C, (int)C, (int)P, (int)ldh, Hd * C,
                        3 * C * P, 3 * Hd * ldh, B, e1, dw.fc1, dw.fc1_b, s));
   } else
-  MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, W1f, x1, h, (int)Hd, (int)P, (int)C, (int)C,
+  MSFNO_TRY(gemm_dense(TILE_128x256, W1f, x1, h, (int)Hd, (int)P, (int)C, (int)C,
                        (int)P, (int)ldh, Hd * C, C * P, (planes ? 3 : 1) * Hd * ldh, B, e1,
                        dw.fc1, dw.fc1_b, s));
   prof(ST_FC2, s);
@@ -1391,7 +1247,7 @@ int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const
     return gemm_x6p(d->fc2_w, out, (int)C, (int)P, (int)Hd, (int)Hd, (int)ldh, (int)P, 0,
                     3 * Hd * ldh, C * P, B, e2, dw.fc2, dw.fc2_b, s);
   }
-  return gemm_dense(ROLE_FC2, TILE_256x128, d->fc2_w, h, out, (int)C, (int)P, (int)Hd, (int)Hd,
+  return gemm_dense(TILE_256x128, d->fc2_w, h, out, (int)C, (int)P, (int)Hd, (int)Hd,
                     (int)ldh, (int)P, 0, (planes ? 3 : 1) * Hd * ldh, C * P, B, e2, dw.fc2,
                     dw.fc2_b, s);
 }
@@ -1421,18 +1277,7 @@ bool skip_x3(const msfno_block_desc* d) {
 
 bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b) {
   return skip_planes_env() && b.x1p && b.dw.skip && d->inner_skip == MSFNO_SKIP_LINEAR &&
-         !use_fft_tile(f) && fft_r2c_planes_supported(f->fft, f->mmax);
-}
-
-// pixels per fc1 -> fc2 chunk of the block MLP (MSFNO_MLP_CHUNK, multiple of 256;
-// 0 = one pass over the field)
-int64_t mlp_chunk(int64_t P) {
-  static const int64_t c = [] {
-    const char* e = getenv("MSFNO_MLP_CHUNK");
-    return e ? (int64_t)atoll(e) / 256 * 256 : (int64_t)0;
-  }();
-  (void)P;
-  return c;
+         fft_r2c_planes_supported(f->fft, f->mmax);
 }
 
 // x1 (the MLP input) written by the inverse FFT as bf16x3 planes: x6 engine, an
@@ -1621,12 +1466,8 @@ int msfno_sht_forward(msfno_sht_plan_t p, const float* x, float* out, int bc, vo
   float* Xt = cv.take<float>((int64_t)p->mmax * R * p->ldk);
   float* S = cv.take<float>(R * p->spec.ldT);
   const float scale = (float)(2.0 * M_PI / p->nlon);
-  if (use_fft_tile(p)) {
-    MSFNO_TRY(launch_fft_r2c_tile(p->fft, x, Xt, nullptr, 1, bc, p->nlat, p->mmax, p->ldk, scale, s));
-  } else {
-    MSFNO_TRY(launch_fft_r2c_rows(p->fft, x, Xn, nullptr, (int64_t)bc * p->nlat, p->mmax, scale, s));
-    MSFNO_TRY(transpose_fwd_plan(p, Xn, Xt, 1, bc, nullptr, nullptr, s));
-  }
+  MSFNO_TRY(launch_fft_r2c_rows(p->fft, x, Xn, nullptr, (int64_t)bc * p->nlat, p->mmax, scale, s));
+  MSFNO_TRY(transpose_fwd_plan(p, Xn, Xt, 1, bc, nullptr, nullptr, s));
   MSFNO_TRY(legendre_fwd(p, Xt, S, (int)R, s));
   MSFNO_TRY(launch_spec_to_ref(*p, S, reinterpret_cast<float2*>(out), 1, bc, p->d_off, s));
   return MSFNO_OK;
@@ -1646,13 +1487,8 @@ int msfno_sht_inverse(msfno_sht_plan_t p, const float* in, float* x, int bc, voi
   float* S = cv.take<float>(R * p->spec.ldT);
   MSFNO_TRY(launch_ref_to_spec(*p, reinterpret_cast<const float2*>(in), S, 1, bc, p->d_off, s));
   MSFNO_TRY(legendre_inv(p, S, Yt, (int)R, s));
-  if (use_fft_tile(p)) {
-    MSFNO_TRY(launch_fft_c2r_tile(p->fft, Yt, x, nullptr, 1, bc, p->nlat, p->mmax, p->spec.mact,
-                                  p->ldk, 0, s));
-  } else {
-    MSFNO_TRY(transpose_inv_plan(p, Yt, Yn, 1, bc, s));
-    MSFNO_TRY(launch_fft_c2r_rows(p->fft, Yn, x, nullptr, nullptr, (int64_t)bc * p->nlat, p->mmax, 0, s));
-  }
+  MSFNO_TRY(transpose_inv_plan(p, Yt, Yn, 1, bc, s));
+  MSFNO_TRY(launch_fft_c2r_rows(p->fft, Yn, x, nullptr, nullptr, (int64_t)bc * p->nlat, p->mmax, 0, s));
   return MSFNO_OK;
 }
 
@@ -1800,7 +1636,7 @@ static int block_forward_impl(const msfno_block_desc* d, msfno_sht_plan_t f, msf
                          3 * C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
     } else {
       // sx: global_conv's skip input is the residual, not the filter input x
-      MSFNO_TRY(gemm_dense(ROLE_SKIP, TILE_128x256, d->skip_w, sx, x1, (int)C, (int)P, (int)C,
+      MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, sx, x1, (int)C, (int)P, (int)C,
                            (int)C, (int)P, (int)P, 0, C * P, C * P, B, e, b.dw.skip, b.dw.skip_b,
                            ss));
     }
@@ -2024,20 +1860,20 @@ int msfno_mlp_forward(const msfno_mlp_desc* d, const float* x, const float* x2,
     e1.act = 1;
     e1.b2 = x2; e1.b2_k = d->Cin; e1.b2_ld = Pi; e1.b2_stride = (int64_t)d->Cin2 * P;
     if (planes) { e1.c_planes = hx; e1.c_plane_stride = Hd * ldh; }
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w, x, h, (int)Hd, Pi, (int)Ct, (int)Ct, Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w, x, h, (int)Hd, Pi, (int)Ct, (int)Ct, Pi,
                          (int)ldh, 0, (int64_t)d->Cin * P, (planes ? 3 : 1) * Hd * ldh, B, e1, w1,
                          w1b, s));
   } else if (d->Cin2 > 0) {
     // fc1 over the concatenation [x ; x2]: t = W1[:, :Cin]·x, then h = GELU(W1[:, Cin:]·x2 + b1 + t)
     GemmEpi e0;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w, x, t, (int)Hd, Pi, d->Cin, (int)Ct, Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w, x, t, (int)Hd, Pi, d->Cin, (int)Ct, Pi,
                          Pi, 0, (int64_t)d->Cin * P, Hd * P, B, e0, w1, w1b, s));
     GemmEpi e1;
     e1.bias = d->fc1_b;
     e1.addend = t; e1.sD = Hd * P; e1.ldd = Pi;
     e1.act = 1;
     if (planes) { e1.c_planes = hx; e1.c_plane_stride = Hd * ldh; }
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w + d->Cin, x2, h, (int)Hd, Pi, d->Cin2,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w + d->Cin, x2, h, (int)Hd, Pi, d->Cin2,
                          (int)Ct, Pi, (int)ldh, 0, (int64_t)d->Cin2 * P,
                          (planes ? 3 : 1) * Hd * ldh, B, e1, w12, w1b2, s));
   } else {
@@ -2045,7 +1881,7 @@ int msfno_mlp_forward(const msfno_mlp_desc* d, const float* x, const float* x2,
     e1.bias = d->fc1_b;
     e1.act = 1;
     if (planes) { e1.c_planes = hx; e1.c_plane_stride = Hd * ldh; }
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w, x, h, (int)Hd, Pi, d->Cin, d->Cin, Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w, x, h, (int)Hd, Pi, d->Cin, d->Cin, Pi,
                          (int)ldh, 0, (int64_t)d->Cin * P, (planes ? 3 : 1) * Hd * ldh, B, e1, w1,
                          w1b, s));
   }
@@ -2064,7 +1900,7 @@ int msfno_mlp_forward(const msfno_mlp_desc* d, const float* x, const float* x2,
     }
   }
   const GemmTile t2 = d->Cout <= 128 ? TILE_128x128 : TILE_256x128;
-  MSFNO_TRY(gemm_dense(ROLE_FC2, t2, d->fc2_w, h, out, d->Cout, Pi, (int)Hd, (int)Hd, (int)ldh, Pi,
+  MSFNO_TRY(gemm_dense(t2, d->fc2_w, h, out, d->Cout, Pi, (int)Hd, (int)Hd, (int)ldh, Pi,
                        0, (planes ? 3 : 1) * Hd * ldh, (int64_t)d->Cout * P, B, e2, w2, w2b, s));
   prof(ST_END, s);
   return MSFNO_OK;
@@ -2150,7 +1986,7 @@ int msfno_block_film_backward(const msfno_block_desc* d, msfno_sht_plan_t f, msf
     MSFNO_REQUIRE(d->skip_w, MSFNO_EINVAL, "missing inner_skip weight");
     GemmEpi e;
     e.bias = d->skip_b;
-    MSFNO_TRY(gemm_dense(ROLE_SKIP, TILE_128x256, d->skip_w, x, x1, (int)C, (int)P, (int)C,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, x, x1, (int)C, (int)P, (int)C,
                          (int)C, (int)P, (int)P, 0, C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, s));
   }
   MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s));
@@ -2174,15 +2010,15 @@ int msfno_block_film_backward(const msfno_block_desc* d, msfno_sht_plan_t f, msf
     GemmEpi e1;  // pre-activation of fc1 (no GELU)
     e1.bias = b.b1f;
     e1.sBias = Hd;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, b.W1f, x1, r.pre, (int)Hd, Pi, (int)C, (int)C,
+    MSFNO_TRY(gemm_dense(TILE_128x256, b.W1f, x1, r.pre, (int)Hd, Pi, (int)C, (int)C,
                          Pi, Pi, Hd * C, C * P, Hd * P, B, e1, b.dw.fc1, b.dw.fc1_b, s));
     MSFNO_TRY(launch_transpose_mat(d->fc2_w, (int)C, (int)Hd, (int)Hd, r.W2T, s));
     GemmEpi e0;
-    MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, r.W2T, dout, r.dh, (int)Hd, Pi, (int)C, (int)C,
+    MSFNO_TRY(gemm_dense(TILE_256x128, r.W2T, dout, r.dh, (int)Hd, Pi, (int)C, (int)C,
                          Pi, Pi, 0, C * P, Hd * P, B, e0, r.wsa, r.wsa_b, s));
     MSFNO_TRY(launch_gelu_grad_mul(r.dh, r.pre, (int64_t)B * Hd * P, s));
     MSFNO_TRY(launch_transpose_mat(d->fc1_w, (int)Hd, (int)C, (int)C, r.W1T, s));
-    MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, r.W1T, r.dh, r.du, (int)C, Pi, (int)Hd, (int)Hd,
+    MSFNO_TRY(gemm_dense(TILE_256x128, r.W1T, r.dh, r.du, (int)C, Pi, (int)Hd, (int)Hd,
                          Pi, Pi, 0, Hd * P, C * P, B, e0, r.wsb, r.wsb_b, s));
     du = r.du;
   }
@@ -2256,24 +2092,24 @@ int msfno_mlp_backward_params(const msfno_mlp_desc* d, const float* x, const flo
   // pre = W1 [x ; x2] + b1 (fc1 without its GELU)
   if (d->Cin2 > 0) {
     GemmEpi e0;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w, x, t, (int)Hd, Pi, d->Cin, (int)Ct, Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w, x, t, (int)Hd, Pi, d->Cin, (int)Ct, Pi,
                          Pi, 0, (int64_t)d->Cin * P, Hd * P, B, e0, w1, w1b, s));
     GemmEpi e1;
     e1.bias = d->fc1_b;
     e1.addend = t; e1.sD = Hd * P; e1.ldd = Pi;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w + d->Cin, x2, pre, (int)Hd, Pi, d->Cin2,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w + d->Cin, x2, pre, (int)Hd, Pi, d->Cin2,
                          (int)Ct, Pi, Pi, 0, (int64_t)d->Cin2 * P, Hd * P, B, e1, w12, w1b2, s));
   } else {
     GemmEpi e1;
     e1.bias = d->fc1_b;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, d->fc1_w, x, pre, (int)Hd, Pi, d->Cin, d->Cin, Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->fc1_w, x, pre, (int)Hd, Pi, d->Cin, d->Cin, Pi,
                          Pi, 0, (int64_t)d->Cin * P, Hd * P, B, e1, w1, w1b, s));
   }
   // dh = GELU'(pre) * W2^T dy ;  dx = W1[:, :Cin]^T dh
   MSFNO_TRY(launch_transpose_mat(d->fc2_w, d->Cout, (int)Hd, (int)Hd, W2T, s));
   GemmEpi e0;
   float* dh = t;
-  MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, W2T, dy, dh, (int)Hd, Pi, d->Cout, d->Cout, Pi, Pi,
+  MSFNO_TRY(gemm_dense(TILE_256x128, W2T, dy, dh, (int)Hd, Pi, d->Cout, d->Cout, Pi, Pi,
                        0, (int64_t)d->Cout * P, Hd * P, B, e0, w2, w2b, s));
   if (params) {
     // dW2 = dy GELU(pre)^T and db2 = sum dy, before dh overwrites pre's partner buffer
@@ -2309,12 +2145,12 @@ int msfno_mlp_backward_params(const msfno_mlp_desc* d, const float* x, const flo
     MSFNO_REQUIRE(x2 && d->Cin2 > 0 && d->Cin2 <= d->Cin, MSFNO_EINVAL,
                   "mlp backward: dx2 needs x2 and Cin2 <= Cin");
     MSFNO_TRY(launch_transpose_mat(d->fc1_w + d->Cin, (int)Hd, d->Cin2, (int)Ct, W1T, s));
-    MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, W1T, dh, dx2, d->Cin2, Pi, (int)Hd, (int)Hd, Pi,
+    MSFNO_TRY(gemm_dense(TILE_256x128, W1T, dh, dx2, d->Cin2, Pi, (int)Hd, (int)Hd, Pi,
                          Pi, 0, Hd * P, (int64_t)d->Cin2 * P, B, e0, w3, w3b, s));
   }
   if (!dx) return MSFNO_OK;
   MSFNO_TRY(launch_transpose_mat(d->fc1_w, (int)Hd, d->Cin, (int)Ct, W1T, s));
-  return gemm_dense(ROLE_FC2, TILE_256x128, W1T, dh, dx, d->Cin, Pi, (int)Hd, (int)Hd, Pi, Pi, 0,
+  return gemm_dense(TILE_256x128, W1T, dh, dx, d->Cin, Pi, (int)Hd, (int)Hd, Pi, Pi, 0,
                     Hd * P, (int64_t)d->Cin * P, B, e0, w3, w3b, s);
 }
 

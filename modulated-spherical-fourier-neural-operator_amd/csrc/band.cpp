@@ -442,7 +442,7 @@ int msfno_band_block_stage(const msfno_block_desc* d, msfno_band_plan_t p, int s
       MSFNO_TRY(gemm_x6p(d->skip_w, b.x1, (int)C, (int)Pl, (int)C, (int)C, (int)Pl, (int)Pl,
                          0, 3 * C * Pl, C * Pl, B, e, b.fb.dw.skip, b.fb.dw.skip_b, ss));
     } else {
-      MSFNO_TRY(gemm_dense(ROLE_SKIP, TILE_128x256, d->skip_w, io->x, b.x1, (int)C, (int)Pl,
+      MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, io->x, b.x1, (int)C, (int)Pl,
                            (int)C, (int)C, (int)Pl, (int)Pl, 0, C * Pl, C * Pl, B, e,
                            b.fb.dw.skip, b.fb.dw.skip_b, ss));
     }

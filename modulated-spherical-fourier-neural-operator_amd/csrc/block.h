@@ -81,8 +81,7 @@ int transpose_fwd_plan(const msfno_sht_plan_s* p, const float2* Xn, float* Xt, i
                        const float* nscale, const float* nshift, hipStream_t s);
 int transpose_inv_plan(const msfno_sht_plan_s* p, const float* Yt, float2* Yn, int B, int C,
                        hipStream_t s);
-int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStream_t s,
-                 const float* rowscale = nullptr, int C = 0);
+int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStream_t s);
 int legendre_inv(msfno_sht_plan_s* g, const float* S, float* Yt, int R, hipStream_t s);
 // spectral filter on S (f->spec layout) in b.Sa (in place)
 bool x3f_usable(msfno_sht_plan_s* f);
@@ -90,9 +89,6 @@ int legendre_fwd_x3f(msfno_sht_plan_s* f, const unsigned short* Xp, const float*
                      int R, hipStream_t s);
 int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
                const BlockBufs& b, int B, hipStream_t s);
-bool use_fft_tile(const msfno_sht_plan_s* p);
-bool use_c3m();
-int c3m_tile();
 void set_table_offsets(msfno_sht_plan_s* p, int sym);
 // channel MLP with norm1/FiLM folded into (W1f, b1f): out = W2·GELU(W1f·x1 + b1f) + b2 (+resid)
 int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const float* x1,
@@ -114,7 +110,6 @@ int run_block_mlp(const msfno_block_desc* d, const float* x1, const unsigned sho
                   const float* sc1, const float* sh1, const float* ab1, float* W1f, float* b1f, float* h,
                   unsigned short* mfimg, float* out, const float* resid, int B, int64_t P,
                   const DenseWs& dw, hipStream_t s);
-int64_t mlp_chunk(int64_t P);
 int64_t mlp_h_floats(int B, int64_t Hd, int64_t P);
 bool x1_planes(const msfno_block_desc* d, const msfno_sht_plan_s* g);
 bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b);

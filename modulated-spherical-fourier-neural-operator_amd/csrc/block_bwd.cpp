@@ -284,7 +284,7 @@ int msfno_block_backward_params(const msfno_block_desc* d, msfno_sht_plan_t f,
     e.addend = r.F;
     e.sD = (int64_t)C * Po;
     e.ldd = (int)Po;
-    MSFNO_TRY(gemm_dense(ROLE_SKIP, TILE_128x256, d->skip_w, x, r.x1pre, C, (int)Po, C, C,
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, x, r.x1pre, C, (int)Po, C, C,
                          (int)Po, (int)Po, 0, (int64_t)C * Pi, (int64_t)C * Po, B, e, r.skws,
                          r.skws_b, s));
   } else {
@@ -315,16 +315,16 @@ int msfno_block_backward_params(const msfno_block_desc* d, msfno_sht_plan_t f,
     GemmEpi e1;
     e1.bias = r.b1f;
     e1.sBias = Hd;
-    MSFNO_TRY(gemm_dense(ROLE_FC1, TILE_128x256, r.W1f, r.x1, r.pre, Hd, Pi2, C, C, Pi2, Pi2,
+    MSFNO_TRY(gemm_dense(TILE_128x256, r.W1f, r.x1, r.pre, Hd, Pi2, C, C, Pi2, Pi2,
                          (int64_t)Hd * C, (int64_t)C * Po, (int64_t)Hd * Po, B, e1, r.wsa,
                          r.wsa_b, s));
     MSFNO_TRY(launch_transpose_mat(d->fc2_w, C, Hd, Hd, r.W2T, s));
     GemmEpi e0;
-    MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, r.W2T, dout, r.dh, Hd, Pi2, C, C, Pi2, Pi2, 0,
+    MSFNO_TRY(gemm_dense(TILE_256x128, r.W2T, dout, r.dh, Hd, Pi2, C, C, Pi2, Pi2, 0,
                          (int64_t)C * Po, (int64_t)Hd * Po, B, e0, r.wsb, r.wsb_b, s));
     MSFNO_TRY(launch_gelu_grad_mul(r.dh, r.pre, (int64_t)B * Hd * Po, s));
     MSFNO_TRY(launch_transpose_mat(d->fc1_w, Hd, C, C, r.W1T, s));
-    MSFNO_TRY(gemm_dense(ROLE_FC2, TILE_256x128, r.W1T, r.dh, r.du, C, Pi2, Hd, Hd, Pi2, Pi2, 0,
+    MSFNO_TRY(gemm_dense(TILE_256x128, r.W1T, r.dh, r.du, C, Pi2, Hd, Hd, Pi2, Pi2, 0,
                          (int64_t)Hd * Po, (int64_t)C * Po, B, e0, r.wsc, r.wsc_b, s));
     du = r.du;
     if (pg) {
@@ -432,7 +432,7 @@ int msfno_block_backward_params(const msfno_block_desc* d, msfno_sht_plan_t f,
     e.addend = r.dxt;
     e.sD = (int64_t)C * Pi;
     e.ldd = (int)Pi;
-    MSFNO_TRY(gemm_dense(ROLE_SKIP, TILE_128x256, r.WsT, r.dx1, dx, C, (int)Pi, C, C, (int)Pi,
+    MSFNO_TRY(gemm_dense(TILE_128x256, r.WsT, r.dx1, dx, C, (int)Pi, C, C, (int)Pi,
                          (int)Pi, 0, (int64_t)C * Po, (int64_t)C * Pi, B, e, r.skws2, r.skws_b,
                          s));
   }

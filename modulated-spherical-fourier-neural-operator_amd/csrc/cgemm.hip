@@ -205,9 +205,16 @@ int launch_split_complex_weight(const float* w, float* Ar, float* Ai, int Ci, in
   return launch_check("split_complex_weight");
 }
 
-template <int BM, int BN>
-static int launch_c3m_t(const C3MParams& p0, int B, bool relu, hipStream_t s) {
-  C3MParams p = p0;
+int gemm_c3m(const float* Ar, const float* Ai, const float* X, float* Y, int co, int ci, int N,
+             int ldx, int ldy, int64_t sX, int64_t sY, int B, bool relu, hipStream_t s) {
+  if (co <= 0 || N <= 0 || B <= 0) return MSFNO_OK;
+  MSFNO_REQUIRE(ci % 4 == 0 && ldx % 4 == 0 && N % 4 == 0, MSFNO_EUNSUPPORTED,
+                "3M spectral GEMM needs ci, ldx and N multiples of 4");
+  MSFNO_REQUIRE(B <= 65535, MSFNO_EINVAL, "gemm_c3m: batch too large");
+  constexpr int BM = 64, BN = 128;  // measured best of 128x64, 64x128, 128x128 (in-block A/B)
+  C3MParams p{};
+  p.Ar = Ar; p.Ai = Ai; p.X = X; p.Y = Y;
+  p.co = co; p.ci = ci; p.N = N; p.ldx = ldx; p.ldy = ldy; p.sX = sX; p.sY = sY;
   p.tiles_m = (int)cdiv(p.co, BM);
   p.tiles_n = (int)cdiv(p.N, BN);
   dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)B);
@@ -216,22 +223,6 @@ static int launch_c3m_t(const C3MParams& p0, int B, bool relu, hipStream_t s) {
   else
     hipLaunchKernelGGL((gemm_c3m_kernel<BM, BN, false>), grid, dim3(256), 0, s, p);
   return launch_check("gemm_c3m");
-}
-
-int gemm_c3m(const float* Ar, const float* Ai, const float* X, float* Y, int co, int ci, int N,
-             int ldx, int ldy, int64_t sX, int64_t sY, int B, bool relu, int tile, hipStream_t s) {
-  if (co <= 0 || N <= 0 || B <= 0) return MSFNO_OK;
-  MSFNO_REQUIRE(ci % 4 == 0 && ldx % 4 == 0 && N % 4 == 0, MSFNO_EUNSUPPORTED,
-                "3M spectral GEMM needs ci, ldx and N multiples of 4");
-  MSFNO_REQUIRE(B <= 65535, MSFNO_EINVAL, "gemm_c3m: batch too large");
-  C3MParams p{};
-  p.Ar = Ar; p.Ai = Ai; p.X = X; p.Y = Y;
-  p.co = co; p.ci = ci; p.N = N; p.ldx = ldx; p.ldy = ldy; p.sX = sX; p.sY = sY;
-  switch (tile) {
-    case 1: return launch_c3m_t<64, 128>(p, B, relu, s);
-    case 2: return launch_c3m_t<128, 128>(p, B, relu, s);
-    default: return launch_c3m_t<128, 64>(p, B, relu, s);
-  }
 }
 
 }  // namespace msfno

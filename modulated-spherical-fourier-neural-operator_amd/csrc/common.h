@@ -119,7 +119,6 @@ struct GemmDesc {
   int lda, ldb, ldc;
   int tiles_m, tiles_n;
   int tile_start;
-  int flags;  // bit 0: apply GemmEpi::rowscale (Legendre-forward m >= 1)
   int64_t offBx, offBs;  // x3h Legendre: the problem's table image / column scales
 };
 
@@ -130,8 +129,6 @@ struct GemmEpi {
   int ldd = 0;
   int act = 0;                      // 0 none, 1 GELU(erf) on C, 2 GELU(erf) on B while staged
   int relu_period = 0, relu_rows = 0;  // ReLU rows where (row % period) < relu_rows
-  const float* rowscale = nullptr;  // per-(b,c) factor for rows r=(b,ri,c); C = rs_C
-  int rs_C = 0;
   // x6 engine only: operands in the bf16x3 plane format (three exact bf16 terms
   // per fp32 value, plane stride in elements; batch stride / ld as for fp32).
   // b_planes replaces B; c_planes receives C (the fp32 C pointer is unused)
@@ -154,15 +151,11 @@ struct GemmEpi {
   int64_t b2_stride = 0;
 };
 
+// ids are stable (tools pass them as numbers).  The fp32 kernel has every tile but
+// 256x256, gemm_x6 has 128x128 and 256x256 (any other id runs on 128x128 there)
 enum GemmTile {
-  TILE_128x128 = 0, TILE_128x64 = 1, TILE_64x64 = 2, TILE_256x64 = 3, TILE_256x128 = 4,
-  TILE_128x256 = 5, TILE_256x256 = 6,  // 256x256: gemm_x6 only
-  TILE_256x32 = 7, TILE_128x32 = 8      // fp32 descriptor (Legendre) GEMMs only
+  TILE_128x128 = 0, TILE_128x64 = 1, TILE_256x128 = 4, TILE_128x256 = 5, TILE_256x256 = 6
 };
-// GEMM role -> tile (defaults chosen by measurement); MSFNO_TILES
-// ("skip=4,fc1=1,...", values = GemmTile) overrides them for A/B experiments
-enum GemmRole { ROLE_SKIP = 0, ROLE_FC1, ROLE_FC2, ROLE_SPEC, ROLE_LEG, ROLE_LEGI, ROLE_COUNT };
-GemmTile role_tile(GemmRole r, GemmTile dflt);
 
 // C[M,N] = A[M,K] · B[K,N] (+ epilogue), row-major, fp32 MFMA.
 // Uniform batched mode: batch index = grid.z, operand batch strides sA/sB/sC.
@@ -174,7 +167,7 @@ int gemm_desc(GemmTile tile, const float* A, const float* B, float* C, const Gem
               int ndesc, int total_tiles, const GemmEpi& epi, hipStream_t s);
 void gemm_tile_dims(GemmTile tile, int* bm, int* bn);
 // fp32-accurate GEMM on the bf16 matrix cores (gemm_x6.hip): same contract as
-// gemm_uniform (no GELU-on-B / rowscale epilogues); ws >= gemm_x6_workspace
+// gemm_uniform (no GELU-on-B epilogue); ws >= gemm_x6_workspace
 // holds A split into bf16 terms (written by this call, stream-ordered)
 size_t gemm_x6_workspace(int M, int K, int batch);
 int gemm_x6(GemmTile tile, const float* A, const float* B, float* C, int M, int N, int K, int lda,
@@ -185,9 +178,8 @@ int launch_split_a(const float* A, unsigned short* Ax, int M, int K, int lda, in
 // the same GEMM on the x3h engine (two fp16 terms, three MFMAs; gemm_x6.hip): B rows
 // scaled by the powers of two bscale[z * K + k] while staged (every |scaled| < 2^14),
 // A re-imaged per batch into ws (>= gemm_x3_workspace); bias-only epilogue
-// x3h Legendre descriptor GEMM (legendre_x3.hip): tiles X3D_BM x x3d_bn(), k-tile X3D_BK
-constexpr int X3D_BM = 128, X3D_BK = 32;
-int x3d_bn(int inverse);
+// x3h Legendre descriptor GEMM (legendre_x3.hip): tiles X3D_BM x X3D_BN, k-tile X3D_BK
+constexpr int X3D_BM = 128, X3D_BN = 64, X3D_BK = 32;
 // register-resident variant (legendre_x3r): every problem K <= X3R_KMAX, N <= X3R_NMAX
 constexpr int X3R_KMAX = 192, X3R_NMAX = 1024;
 // register-B forward variant (legendre_x3f): K <= X3F_KMAX, X3F_RB rows x 64 columns per tile
@@ -195,7 +187,7 @@ constexpr int X3F_KMAX = 384, X3F_RB = 256;
 int launch_legendre_x3_image(const float* table, const GemmDesc* descs, int ndesc,
                              unsigned short* img, float* invs, hipStream_t s);
 int legendre_x3(const float* A, const unsigned short* img, const float* invs, float* C,
-                const GemmDesc* descs, const int* tile_desc, int ndesc, int tiles, int bn,
+                const GemmDesc* descs, const int* tile_desc, int ndesc, int tiles,
                 const GemmEpi& e, hipStream_t s);
 int legendre_x3f(const unsigned short* Ap, const float* isr,
                  const unsigned short* img, const float* invs, float* C, const GemmDesc* descs,
@@ -212,10 +204,6 @@ int gemm_x3(const float* A, int lda, const float* bscale, const float* B, float*
 // epi.b_planes required (ldb, sB, b_plane_stride % 8 == 0, 16-B aligned); A fp32
 // is split per call into ws (>= gemm_x6p_workspace(M, K, sA == 0 ? 1 : batch))
 size_t gemm_x6p_workspace(int M, int K, int batch_a);
-// the A image of gemm_x6p (16-deep k-tiles) split once into ws, for a sequence of
-// gemm_x6p calls that pass it as epi.a_planes (e.g. pixel-chunked MLPs)
-int gemm_x6p_split_a(const float* A, int M, int K, int lda, int64_t sA, int batch, void* ws,
-                     size_t ws_bytes, hipStream_t s);
 int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, int ldc,
              int64_t sA, int64_t sB, int64_t sC, int batch, const GemmEpi& epi, void* ws,
              size_t ws_bytes, hipStream_t s);
@@ -239,14 +227,13 @@ int launch_spec_weights_x6p(const SpecWeightsX6p& a, hipStream_t s);
 size_t gemm_x6c_weight_bytes(int co, int ci);
 size_t spec_weights_3m_layout(SpecWeightsX6p& a);
 int launch_spec_weights_3m(const SpecWeightsX6p& a, hipStream_t s);
-int launch_split3m(const float* S, unsigned short* X, int B, int C, int N, int ldS, int ldx,
-                   hipStream_t s);
+// layer 0: fp32 rows in (split while staged), tiled planes out; later layers: tiled
+// planes in, tiled planes Y or fp32 rows S out
 int gemm_x6c_f32b(const unsigned short* Aw, int co, int ci, const float* Sin, int ldSin, int N,
-                  unsigned short* Y, int ldy, float* Sout, int ldSout, bool relu, int B,
-                  hipStream_t s, bool tiled_out = false);
+                  unsigned short* Y, int ldy, bool relu, int B, hipStream_t s);
 int64_t x6c_tiled_elems(int rows, int N);
 int gemm_x6c(const unsigned short* Aw, int co, int ci, const unsigned short* X, int N, int ldx,
-             unsigned short* Y, float* S, int ldS, bool relu, int B, hipStream_t s, int lay = 0);
+             unsigned short* Y, float* S, int ldS, bool relu, int B, hipStream_t s);
 // the same chain on the x3h engine (two fp16 terms, three MFMAs per product; tiled
 // hidden activations of 6 planes).  Scaling (all powers of two): the weights of layer
 // l by a.scl[2l] (spec_scales_x3h_kernel), layer 0's input column (b, n) by
@@ -266,11 +253,11 @@ int launch_split_planes(const float* x, unsigned short* xp, int rows, int cols, 
                         int64_t sx, int ldp, int64_t pstride, int64_t sxp, int batch,
                         hipStream_t s);
 // dense 1x1-conv GEMMs of the block / MLP: gemm_x6 unless MSFNO_GEMM=f32 (or no
-// workspace / a GELU-on-B or rowscale epilogue), else the fp32 MFMA kernel on
-// role_tile(role, f32_tile).  batch_a = 1 when sA == 0, else batch.
+// workspace / a GELU-on-B epilogue), else the fp32 MFMA kernel on f32_tile
+// (chosen by measurement).  batch_a = 1 when sA == 0, else batch.
 bool gemm_use_x6();
 size_t gemm_dense_workspace(int M, int K, int batch_a);
-int gemm_dense(GemmRole role, GemmTile f32_tile, const float* A, const float* B, float* C, int M,
+int gemm_dense(GemmTile f32_tile, const float* A, const float* B, float* C, int M,
                int N, int K, int lda, int ldb, int ldc, int64_t sA, int64_t sB, int64_t sC,
                int batch, const GemmEpi& epi, void* ws, size_t ws_bytes, hipStream_t s);
 

@@ -1072,216 +1072,6 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
   }
 }
 
-// ---------------------------------------------------------------------------
-// Fused FFT + transpose kernels (the block's path).  A workgroup owns TK
-// consecutive latitudes of one (b,c) plane; each wave transforms TK/4 rows with
-// the next row's global loads in flight (register prefetch) while it computes.
-//   forward: x rows -> LDS tile [m][TK] -> Xt[m][(b,ri,c)][k0..k0+TK)   (m-major
-//            GEMM operand of the Legendre stage; spectrum NOT normalised: the
-//            InstanceNorm-0 affine is applied later, see dc_fixup / GEMM rowscale)
-//   inverse: Yt[m][(b,ri,c)][k0..) -> LDS tile [m][TK] -> irfft rows -> output
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int xcd_remap_1d(int orig, int nwg) {
-  const int xcd = orig & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-}
-
-// LDS tile: separate real / imaginary planes [mmax][TK + pad] so that four
-// consecutive latitudes move as one float4 between LDS and HBM.
-template <int TK>
-struct TileGeom {
-  static constexpr int TS = TK + 4;  // plane row stride (floats), keeps float4 alignment
-};
-
-template <class CL, int TK>
-__global__ __launch_bounds__(256) void fft_r2c_tile_kernel(const float* __restrict__ x,
-                                                           float* __restrict__ Xt,
-                                                           float2* __restrict__ rowstats, int C,
-                                                           int nlat, int mmax, int ldk, int64_t R,
-                                                           int ntiles, float scale, FFTArgs f) {
-  extern __shared__ float2 smem[];
-  constexpr int H = CL::H;
-  constexpr int N = 2 * H;
-  constexpr int NV = (N / 4 + 63) / 64;
-  constexpr int TS = TileGeom<TK>::TS;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  float2* tw = smem;
-  float* pre = reinterpret_cast<float*>(smem + H);
-  float* pim = pre + (size_t)mmax * TS;
-  float2* buf = reinterpret_cast<float2*>(pim + (size_t)mmax * TS) + (size_t)w * H;
-  load_twiddles(tw, f);
-  const int lin = xcd_remap_1d(blockIdx.x, gridDim.x);
-  const int tile = lin % ntiles;
-  const int bc = lin / ntiles;
-  const int k0 = tile * TK;
-  const float4* plane = reinterpret_cast<const float4*>(x + (int64_t)bc * nlat * N);
-  float4 pf[NV];
-  auto prefetch = [&](int kk) {
-    const int k = k0 + kk;
-    if (kk < TK && k < nlat) {
-      const float4* r4 = plane + (int64_t)k * (N / 4);
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        const int n = lane + 64 * j;
-        if (n < N / 4) pf[j] = r4[n];
-      }
-    }
-  };
-  prefetch(w);
-  for (int kk = w; kk < TK && k0 + kk < nlat; kk += 4) {
-    const int k = k0 + kk;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int n = lane + 64 * j;
-      if (n < N / 4) {
-        const float4 v = pf[j];
-        buf[2 * n] = make_float2(v.x, v.y);
-        buf[2 * n + 1] = make_float2(v.z, v.w);
-        s += (v.x + v.y) + (v.z + v.w);
-      }
-    }
-    prefetch(kk + 4);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (rowstats) {
-      const float mean = wave_sum(s) / (float)N;
-      float q = 0.f;
-      for (int n = lane; n < H; n += 64) {
-        const float2 v = buf[n];
-        q += (v.x - mean) * (v.x - mean) + (v.y - mean) * (v.y - mean);
-      }
-      q = wave_sum(q);
-      if (lane == 0) rowstats[(int64_t)bc * nlat + k] = make_float2(mean, q);
-    }
-    CL::template run<false>(buf, nullptr, f, tw, lane);
-    for (int m = lane; m < mmax; m += 64) {
-      const float2 zk = buf[m % H];
-      const float2 zc = cconj(buf[(H - m) % H]);
-      const float2 E = make_float2(0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y));
-      const float2 D = csub(zk, zc);
-      const float2 O = make_float2(0.5f * D.y, -0.5f * D.x);
-      const float2 X = cadd(E, cmul(f.twN[m], O));
-      pre[m * TS + kk] = scale * X.x;
-      pim[m * TS + kk] = scale * X.y;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
-  __syncthreads();
-  const int b = bc / C, c = bc - b * C;
-  const int64_t rre = (int64_t)(b * 2) * C + c, rim = rre + C;
-  constexpr int Q = TK / 4;
-  const int total = mmax * 2 * Q;
-  for (int e = threadIdx.x; e < total; e += 256) {
-    const int m = e / (2 * Q);
-    const int rem = e - m * 2 * Q;
-    const int ri = rem / Q, q = rem - ri * Q;
-    const int k = k0 + 4 * q;
-    if (k < nlat) {  // k < nlat <= ldk, ldk % 4 == 0: the float4 stays inside the row
-      const float4 v = *reinterpret_cast<const float4*>((ri ? pim : pre) + m * TS + 4 * q);
-      *reinterpret_cast<float4*>(Xt + ((int64_t)m * R + (ri ? rim : rre)) * ldk + k) = v;
-    }
-  }
-}
-
-template <class CL, int TK>
-__global__ __launch_bounds__(256) void fft_c2r_tile_kernel(const float* __restrict__ Yt,
-                                                           float* __restrict__ out,
-                                                           float2* __restrict__ rowstats, int C,
-                                                           int nlat, int mmax, int mact, int ldk,
-                                                           int64_t R, int ntiles, int act,
-                                                           FFTArgs f) {
-  extern __shared__ float2 smem[];
-  constexpr int H = CL::H;
-  constexpr int N = 2 * H;
-  constexpr int TS = TileGeom<TK>::TS;
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  float2* tw = smem;
-  float* pre = reinterpret_cast<float*>(smem + H);
-  float* pim = pre + (size_t)mmax * TS;
-  float2* buf = reinterpret_cast<float2*>(pim + (size_t)mmax * TS) + (size_t)w * H;
-  const int lin = xcd_remap_1d(blockIdx.x, gridDim.x);
-  const int tile = lin % ntiles;
-  const int bc = lin / ntiles;
-  const int k0 = tile * TK;
-  const int b = bc / C, c = bc - b * C;
-  const int64_t rre = (int64_t)(b * 2) * C + c, rim = rre + C;
-  for (int t = threadIdx.x; t < H; t += 256) tw[t] = f.twH[t];
-  constexpr int Q = TK / 4;
-  const int total = mmax * 2 * Q;
-  // all loads of the tile issued before any LDS write (kLoadBatch in flight per lane)
-  constexpr int kLoadBatch = 8;
-  for (int e0 = 0; e0 < total; e0 += 256 * kLoadBatch) {
-    float4 v[kLoadBatch];
-#pragma unroll
-    for (int u = 0; u < kLoadBatch; ++u) {
-      const int e = e0 + u * 256 + threadIdx.x;
-      const int m = e / (2 * Q);
-      const int rem = e - m * 2 * Q;
-      const int ri = rem / Q, q = rem - ri * Q;
-      const int k = k0 + 4 * q;
-      v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (e < total && k < nlat && m < mact)
-        v[u] = *reinterpret_cast<const float4*>(Yt + ((int64_t)m * R + (ri ? rim : rre)) * ldk + k);
-    }
-#pragma unroll
-    for (int u = 0; u < kLoadBatch; ++u) {
-      const int e = e0 + u * 256 + threadIdx.x;
-      if (e < total) {
-        const int m = e / (2 * Q);
-        const int rem = e - m * 2 * Q;
-        const int ri = rem / Q, q = rem - ri * Q;
-        *reinterpret_cast<float4*>((ri ? pim : pre) + m * TS + 4 * q) = v[u];
-      }
-    }
-  }
-  __syncthreads();
-  for (int kk = w; kk < TK && k0 + kk < nlat; kk += 4) {
-    const int k = k0 + kk;
-    for (int q = lane; q < H; q += 64) {
-      float2 xk = q < mmax ? make_float2(pre[q * TS + kk], pim[q * TS + kk]) : make_float2(0.f, 0.f);
-      if (q == 0) xk.y = 0.f;
-      const int q2 = H - q;
-      float2 xh = q2 < mmax ? make_float2(pre[q2 * TS + kk], pim[q2 * TS + kk]) : make_float2(0.f, 0.f);
-      if (q2 == H || q2 == 0) xh.y = 0.f;
-      const float2 xc = cconj(xh);
-      const float2 A = cadd(xk, xc);
-      const float2 D = csub(xk, xc);
-      const float2 T = cmul(cconj(f.twN[q]), D);
-      buf[q] = make_float2(A.x - T.y, A.y + T.x);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    CL::template run<true>(buf, nullptr, f, tw, lane);
-    float4* o4 = reinterpret_cast<float4*>(out + ((int64_t)bc * nlat + k) * N);
-    float s = 0.f;
-    for (int n = lane; n < N / 4; n += 64) {
-      float2 a = buf[2 * n], bb = buf[2 * n + 1];
-      if (act == 1) {
-        a.x = gelu_erf_f(a.x); a.y = gelu_erf_f(a.y);
-        bb.x = gelu_erf_f(bb.x); bb.y = gelu_erf_f(bb.y);
-        buf[2 * n] = a;
-        buf[2 * n + 1] = bb;
-      }
-      o4[n] = make_float4(a.x, a.y, bb.x, bb.y);
-      s += (a.x + a.y) + (bb.x + bb.y);
-    }
-    if (rowstats) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      const float mean = wave_sum(s) / (float)N;
-      float q = 0.f;
-      for (int n = lane; n < H; n += 64) {
-        const float2 v = buf[n];
-        q += (v.x - mean) * (v.x - mean) + (v.y - mean) * (v.y - mean);
-      }
-      q = wave_sum(q);
-      if (lane == 0) rowstats[(int64_t)bc * nlat + k] = make_float2(mean, q);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  }
-}
-
 static FFTArgs make_args(const FFTPlan& p) {
   FFTArgs a{};
   a.N = p.N; a.H = p.H; a.packed = p.packed; a.nrad = p.nrad; a.inplace = p.inplace;
@@ -1503,93 +1293,10 @@ bool fft_c2r_planes_supported(const FFTPlan& f, int mmax) {
          ncy <= 5;
 }
 
-template <class CL, int TK>
-static size_t tile_lds(int mmax) {
-  return (size_t)CL::H * 5 * sizeof(float2) + (size_t)2 * mmax * TileGeom<TK>::TS * sizeof(float);
-}
-
 static int set_lds_limit(const void* fn, size_t lds) {
   if (lds > 64 * 1024)
     MSFNO_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return MSFNO_OK;
-}
-
-static int tile_k() {
-  static int tk = -1;
-  if (tk < 0) {
-    const char* e = getenv("MSFNO_FFT_TK");
-    tk = (e && atoi(e) == 8) ? 8 : 16;
-  }
-  return tk;
-}
-
-template <class CL, int TK>
-static int launch_r2c_tile_t(const FFTArgs& a, const float* x, float* Xt, float2* rowstats, int B,
-                             int C, int nlat, int mmax, int ldk, float scale, hipStream_t s) {
-  const size_t lds = tile_lds<CL, TK>(mmax);
-  MSFNO_REQUIRE(lds <= 160 * 1024, MSFNO_EUNSUPPORTED, "FFT tile exceeds LDS");
-  MSFNO_TRY(set_lds_limit(reinterpret_cast<const void*>(&fft_r2c_tile_kernel<CL, TK>), lds));
-  const int ntiles = (int)cdiv(nlat, TK);
-  hipLaunchKernelGGL((fft_r2c_tile_kernel<CL, TK>), dim3((unsigned)(ntiles * B * C)), dim3(256),
-                     lds, s, x, Xt, rowstats, C, nlat, mmax, ldk, 2LL * B * C, ntiles, scale, a);
-  return launch_check("fft_r2c_tile");
-}
-
-template <class CL, int TK>
-static int launch_c2r_tile_t(const FFTArgs& a, const float* Yt, float* out, float2* rowstats,
-                             int B, int C, int nlat, int mmax, int mact, int ldk, int act,
-                             hipStream_t s) {
-  const size_t lds = tile_lds<CL, TK>(mmax);
-  MSFNO_REQUIRE(lds <= 160 * 1024, MSFNO_EUNSUPPORTED, "FFT tile exceeds LDS");
-  MSFNO_TRY(set_lds_limit(reinterpret_cast<const void*>(&fft_c2r_tile_kernel<CL, TK>), lds));
-  const int ntiles = (int)cdiv(nlat, TK);
-  hipLaunchKernelGGL((fft_c2r_tile_kernel<CL, TK>), dim3((unsigned)(ntiles * B * C)), dim3(256),
-                     lds, s, Yt, out, rowstats, C, nlat, mmax, mact, ldk, 2LL * B * C, ntiles, act,
-                     a);
-  return launch_check("fft_c2r_tile");
-}
-
-template <class CL>
-static int launch_r2c_tile(const FFTArgs& a, const float* x, float* Xt, float2* rowstats, int B,
-                           int C, int nlat, int mmax, int ldk, float scale, hipStream_t s) {
-  return tile_k() == 8
-             ? launch_r2c_tile_t<CL, 8>(a, x, Xt, rowstats, B, C, nlat, mmax, ldk, scale, s)
-             : launch_r2c_tile_t<CL, 16>(a, x, Xt, rowstats, B, C, nlat, mmax, ldk, scale, s);
-}
-
-template <class CL>
-static int launch_c2r_tile(const FFTArgs& a, const float* Yt, float* out, float2* rowstats,
-                           int B, int C, int nlat, int mmax, int mact, int ldk, int act,
-                           hipStream_t s) {
-  return tile_k() == 8
-             ? launch_c2r_tile_t<CL, 8>(a, Yt, out, rowstats, B, C, nlat, mmax, mact, ldk, act, s)
-             : launch_c2r_tile_t<CL, 16>(a, Yt, out, rowstats, B, C, nlat, mmax, mact, ldk, act, s);
-}
-
-bool fft_tile_supported(const FFTPlan& f) { return f.codelet != 0 && (f.N % 4) == 0; }
-
-int launch_fft_r2c_tile(const FFTPlan& f, const float* x, float* Xt, float2* rowstats, int B,
-                        int C, int nlat, int mmax, int ldk, float scale, hipStream_t s) {
-  const FFTArgs a = make_args(f);
-  switch (f.codelet) {
-#define X(id, CL) \
-  case id: return launch_r2c_tile<CL>(a, x, Xt, rowstats, B, C, nlat, mmax, ldk, scale, s);
-    MSFNO_FFT_CODELETS(X)
-#undef X
-    default: set_error("no FFT codelet for this nlon"); return MSFNO_EUNSUPPORTED;
-  }
-}
-
-int launch_fft_c2r_tile(const FFTPlan& f, const float* Yt, float* out, float2* rowstats, int B,
-                        int C, int nlat, int mmax, int mact, int ldk, int act, hipStream_t s) {
-  const FFTArgs a = make_args(f);
-  switch (f.codelet) {
-#define X(id, CL) \
-  case id: return launch_c2r_tile<CL>(a, Yt, out, rowstats, B, C, nlat, mmax, mact, ldk, act, s);
-    MSFNO_FFT_CODELETS(X)
-#undef X
-    default: set_error("no FFT codelet for this nlon"); return MSFNO_EUNSUPPORTED;
-  }
 }
 
 template <int... Rs>

@@ -54,7 +54,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
   int tm, tn;
   const float* bias = p.bias;
   const float* addend = p.addend;
-  int dflags = 0;
   if (p.descs) {
     const int lin = xcd_remap(blockIdx.x, gridDim.x);
     int lo = 0, hi = p.ndesc - 1;
@@ -65,7 +64,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     const GemmDesc d = p.descs[lo];
     A += d.offA; B += d.offB; C += d.offC;
     M = d.M; N = d.N; K = d.K; lda = d.lda; ldb = d.ldb; ldc = d.ldc;
-    dflags = d.flags;
     const int local = lin - d.tile_start;
     tm = local % d.tiles_m;
     tn = local / d.tiles_m;
@@ -257,46 +255,17 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmParams p) {
     }
   }
 
-  gemm_epilogue<BM, BN, EPI, WGM, WGN>(p, acc, lds, bias_s, C, addend, M, N, ldc, m0, n0, dflags);
+  gemm_epilogue<BM, BN, EPI, WGM, WGN>(p, acc, lds, bias_s, C, addend, M, N, ldc, m0, n0);
 }
 
-GemmTile role_tile(GemmRole r, GemmTile dflt) {
-  static int table[ROLE_COUNT];
-  static bool init = false;
-  if (!init) {
-    for (int& t : table) t = -1;
-    if (const char* e = getenv("MSFNO_TILES")) {
-      static const char* names[ROLE_COUNT] = {"skip", "fc1", "fc2", "spec", "leg", "legi"};
-      std::string spec(e);
-      size_t pos = 0;
-      while (pos < spec.size()) {
-        size_t end = spec.find(',', pos);
-        if (end == std::string::npos) end = spec.size();
-        const std::string kv = spec.substr(pos, end - pos);
-        const size_t eq = kv.find('=');
-        if (eq != std::string::npos)
-          for (int i = 0; i < ROLE_COUNT; ++i)
-            if (kv.substr(0, eq) == names[i]) table[i] = atoi(kv.c_str() + eq + 1);
-        pos = end + 1;
-      }
-    }
-    init = true;
-  }
-  const int t = table[r];
-  return (t >= 0 && t <= TILE_128x32) ? (GemmTile)t : dflt;
-}
-
+// the fp32 instances: the tiles the call sites name
 void gemm_tile_dims(GemmTile tile, int* bm, int* bn) {
   switch (tile) {
-    case TILE_128x128: *bm = 128; *bn = 128; break;
     case TILE_128x64: *bm = 128; *bn = 64; break;
-    case TILE_256x64: *bm = 256; *bn = 64; break;
     case TILE_256x128: *bm = 256; *bn = 128; break;
     case TILE_128x256: *bm = 128; *bn = 256; break;
-    case TILE_256x256: *bm = 256; *bn = 256; break;
-    case TILE_256x32: *bm = 256; *bn = 32; break;
-    case TILE_128x32: *bm = 128; *bn = 32; break;
-    default: *bm = 64; *bn = 64; break;
+    case TILE_256x256: *bm = 256; *bn = 256; break;  // gemm_x6 only
+    default: *bm = 128; *bn = 128; break;
   }
 }
 
@@ -306,8 +275,6 @@ static GemmParams make_params(const float* A, const float* B, float* C, const Ge
   p.bias = e.bias; p.addend = e.addend;
   p.sBias = e.sBias; p.sD = e.sD;
   p.ldd = e.ldd; p.act = e.act; p.relu_period = e.relu_period; p.relu_rows = e.relu_rows;
-  p.rowscale = e.rowscale;
-  p.rs_C = e.rs_C;
   p.segA_w = e.segA_w; p.segA_stride = e.segA_stride;
   p.segC_w = e.segC_w; p.segC_stride = e.segC_stride;
   return p;
@@ -325,22 +292,7 @@ static void launch_e(const GemmParams& p, dim3 grid, hipStream_t s) {
 
 static int epi_code(const GemmParams& p) {
   return (p.bias ? EPI_BIAS : 0) | (p.addend ? EPI_ADD : 0) | (p.act == 1 ? EPI_GELU : 0) |
-         (p.relu_period ? EPI_RELU : 0) |
-         (p.rowscale ? EPI_ROWSCALE : 0) | (p.act == 2 ? EPI_GELU_B : 0);
-}
-
-// the 32-column tiles (4 x 1 waves): the Legendre descriptor GEMMs only (no epilogue
-// or the forward row scale)
-template <int BM, int BN, int BK>
-static int launch_narrow(const GemmParams& p, dim3 grid, hipStream_t s) {
-  switch (epi_code(p)) {
-    case 0: launch_e<BM, BN, BK, 0, 4>(p, grid, s); break;
-    case EPI_ROWSCALE: launch_e<BM, BN, BK, EPI_ROWSCALE, 4>(p, grid, s); break;
-    default:
-      set_error("gemm: 32-column tiles take no epilogue");
-      return MSFNO_EUNSUPPORTED;
-  }
-  return MSFNO_OK;
+         (p.relu_period ? EPI_RELU : 0) | (p.act == 2 ? EPI_GELU_B : 0);
 }
 
 // the epilogue combinations the block uses (anything else is rejected)
@@ -349,7 +301,6 @@ static int launch(const GemmParams& p, dim3 grid, hipStream_t s) {
   switch (epi_code(p)) {
     case 0: launch_e<BM, BN, BK, 0>(p, grid, s); break;
     case EPI_RELU: launch_e<BM, BN, BK, EPI_RELU>(p, grid, s); break;
-    case EPI_ROWSCALE: launch_e<BM, BN, BK, EPI_ROWSCALE>(p, grid, s); break;
     case EPI_BIAS: launch_e<BM, BN, BK, EPI_BIAS>(p, grid, s); break;
     case EPI_BIAS | EPI_GELU: launch_e<BM, BN, BK, EPI_BIAS | EPI_GELU>(p, grid, s); break;
     case EPI_BIAS | EPI_ADD: launch_e<BM, BN, BK, EPI_BIAS | EPI_ADD>(p, grid, s); break;
@@ -375,12 +326,11 @@ static int dispatch(GemmTile tile, const GemmParams& p, dim3 grid, hipStream_t s
   switch (tile) {
     case TILE_128x128: rc = launch<128, 128, MSFNO_GEMM_BK>(p, grid, s); break;
     case TILE_128x64: rc = launch<128, 64, MSFNO_GEMM_BK>(p, grid, s); break;
-    case TILE_256x64: rc = launch<256, 64, MSFNO_GEMM_BK>(p, grid, s); break;
     case TILE_256x128: rc = launch<256, 128, MSFNO_GEMM_BK>(p, grid, s); break;
     case TILE_128x256: rc = launch<128, 256, MSFNO_GEMM_BK>(p, grid, s); break;
-    case TILE_256x32: rc = launch_narrow<256, 32, MSFNO_GEMM_BK>(p, grid, s); break;
-    case TILE_128x32: rc = launch_narrow<128, 32, MSFNO_GEMM_BK>(p, grid, s); break;
-    default: rc = launch<64, 64, MSFNO_GEMM_BK>(p, grid, s); break;
+    default:
+      set_error("gemm: no fp32 instance of this tile");
+      return MSFNO_EUNSUPPORTED;
   }
   if (rc != MSFNO_OK) return rc;
   return launch_check("gemm_f32");

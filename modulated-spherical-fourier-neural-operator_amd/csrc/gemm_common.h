@@ -25,8 +25,6 @@ struct GemmParams {
   int64_t sBias, sD;
   int ldd, act, relu_period, relu_rows;
   int vecC;  // C (and addend) rows 16-B aligned: float4 epilogue loads/stores
-  const float* rowscale;
-  int rs_C;
   // gemm_x6: A pre-split into 3 bf16 planes [batch][3][Mp][Kp] (k contiguous)
   const unsigned short* Ax;
   int64_t sAx, sAxp;  // batch stride, plane stride (elements)
@@ -146,7 +144,7 @@ inline bool cx16_enabled() {
 
 // epilogue flags (+ EPI_GELU_B: GELU applied to the B operand while it is staged)
 enum : int {
-  EPI_BIAS = 1, EPI_ADD = 2, EPI_GELU = 4, EPI_RELU = 8, EPI_ROWSCALE = 32, EPI_GELU_B = 64,
+  EPI_BIAS = 1, EPI_ADD = 2, EPI_GELU = 4, EPI_RELU = 8, EPI_GELU_B = 64,
   EPI_PLANES = 128  // store C as three exact bf16 terms (the x6 operand format)
 };
 
@@ -163,7 +161,7 @@ template <int BM, int BN, int EPI, int WGM = 2, int WGN = 2, int MT, int NT, int
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, AccV (&acc)[MT][NT],
                                               float* lds, const float* bias_s, float* C,
                                               const float* addend, int M, int N, int ldc,
-                                              int m0, int n0, int dflags) {
+                                              int m0, int n0) {
   constexpr int NTHR = 64 * WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN;
   static_assert(MT == WM / RB && NT == WN / RB, "accumulator shape");
@@ -172,7 +170,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, AccV (&acc)[M
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
   const int half = lane >> 5, l32 = lane & 31;
-  (void)bias_s; (void)addend; (void)dflags; (void)half; (void)l32;
+  (void)bias_s; (void)addend; (void)half; (void)l32;
   // ---- epilogue through LDS ---------------------------------------------------
   // Per MFMA row-tile i the waves write their 32-row slices into a (32 WGM) x BN
   // row-major LDS image; then all threads walk it with 16-B vectors: bias,
@@ -253,12 +251,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, AccV (&acc)[M
         const int row = m0 + (lr / RB) * WM + i * RB + (lr % RB);
         const int col = n0 + 4 * c4;
         float4 v = cv[q];
-        const int rr = min(row, M - 1);
-        if constexpr ((EPI & EPI_ROWSCALE) != 0) {
-          const int C2 = 2 * p.rs_C;
-          const float sv = (dflags & 1) ? p.rowscale[(rr / C2) * p.rs_C + rr % p.rs_C] : 1.f;
-          v.x *= sv; v.y *= sv; v.z *= sv; v.w *= sv;
-        }
         if constexpr ((EPI & EPI_BIAS) != 0) {
           const float bv = bvq[q];
           v.x += bv; v.y += bv; v.z += bv; v.w += bv;

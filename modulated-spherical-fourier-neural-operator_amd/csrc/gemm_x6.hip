@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6_kernel(GemmParams p) {
       }
   }
   gemm_epilogue<BM, BN, EPI, WGM, WGN>(p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C, addend, M, N,
-                             ldc, m0, n0, 0);
+                             ldc, m0, n0);
 }
 
 // ---- host ---------------------------------------------------------------------
@@ -348,14 +348,8 @@ size_t gemm_dense_workspace(int M, int K, int batch_a) {
 
 // 256x256 (8 waves) when the grid still fills the chip twice over, else 128x128;
 // M <= 128 always takes 128x128 (a 256-row tile would pad the MFMA work: the
-// decoder's 256 -> 73 fc2 runs 0.61-0.66 ms on 128x128 vs 0.93 ms on 256x256).
-// MSFNO_X6_TILE=<GemmTile id> overrides for experiments
+// decoder's 256 -> 73 fc2 runs 0.61-0.66 ms on 128x128 vs 0.93 ms on 256x256)
 static GemmTile x6_tile(int M, int N, int batch) {
-  static const int forced = [] {
-    const char* e = getenv("MSFNO_X6_TILE");
-    return e ? atoi(e) : -1;
-  }();
-  if (forced >= 0 && forced <= TILE_256x256) return (GemmTile)forced;
   if (M <= 128) return TILE_128x128;
   const int64_t big = cdiv(M, 256) * cdiv(N, 256) * (int64_t)batch;
   return big >= 512 ? TILE_256x256 : TILE_128x128;
@@ -384,7 +378,7 @@ template <int BM, int BN, int WGM, int WGN>
 static int launch_x6(const GemmParams& p, dim3 grid, hipStream_t s) {
   const int code = (p.bias ? EPI_BIAS : 0) | (p.addend ? EPI_ADD : 0) | (p.act == 1 ? EPI_GELU : 0) |
                    (p.relu_period ? EPI_RELU : 0) | (p.Cx ? EPI_PLANES : 0);
-  if (p.act == 2 || p.rowscale) {
+  if (p.act == 2) {
     set_error("gemm_x6: unsupported epilogue");
     return MSFNO_EUNSUPPORTED;
   }
@@ -437,7 +431,6 @@ int gemm_x6(GemmTile tile, const float* A, const float* B, float* C, int M, int 
   p.sB = sB; p.sC = sC;
   p.bias = epi.bias; p.addend = epi.addend; p.sBias = epi.sBias; p.sD = epi.sD;
   p.ldd = epi.ldd; p.act = epi.act; p.relu_period = epi.relu_period; p.relu_rows = epi.relu_rows;
-  p.rowscale = epi.rowscale;
   p.Ax = Ax; p.sAxp = (int64_t)Mp * Kp; p.sAx = sA == 0 ? 0 : 3 * p.sAxp; p.ldax = Kp;
   p.vecB = (ldb % 4 == 0) && (sB % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0);
   p.B2 = epi.b2; p.kb2 = epi.b2_k; p.ldb2 = epi.b2_ld; p.sB2 = epi.b2_stride;
@@ -462,11 +455,11 @@ int gemm_x6(GemmTile tile, const float* A, const float* B, float* C, int M, int 
   p.vecC = (ldc % 4 == 0) && (sC % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) &&
            (!epi.addend || ((epi.ldd % 4 == 0) && (epi.sD % 4 == 0) &&
                             ((reinterpret_cast<uintptr_t>(epi.addend) & 15) == 0)));
-  // tile -> (BM, BN, wave grid): 128x128 4 waves, 256x128 8 waves (4x2),
-  // 128x256 4 waves, 256x256 8 waves (4x2)
+  // tile -> (BM, BN, wave grid): 128x128 4 waves, 256x256 8 waves (4x2); x6_tile returns
+  // no other, any other id runs on 128x128
   int bm, bn;
   gemm_tile_dims(tile, &bm, &bn);
-  if (tile != TILE_256x128 && tile != TILE_128x256 && tile != TILE_256x256) {
+  if (tile != TILE_256x256) {
     tile = TILE_128x128; bm = bn = 128;
   }
   p.tiles_m = (int)cdiv(M, bm);
@@ -474,8 +467,6 @@ int gemm_x6(GemmTile tile, const float* A, const float* B, float* C, int M, int 
   const dim3 grid(p.tiles_m * p.tiles_n, 1, batch);
   int rc;
   switch (tile) {
-    case TILE_256x128: rc = launch_x6<256, 128, 4, 2>(p, grid, s); break;
-    case TILE_128x256: rc = launch_x6<128, 256, 2, 2>(p, grid, s); break;
     case TILE_256x256: rc = launch_x6<256, 256, 4, 2>(p, grid, s); break;
     default: rc = launch_x6<128, 128, 2, 2>(p, grid, s); break;
   }
@@ -553,7 +544,7 @@ int gemm_x3(const float* A, int lda, const float* bscale, const float* B, float*
   MSFNO_REQUIRE(ws && ws_bytes >= gemm_x3_workspace(M, K, batch), MSFNO_EINVAL,
                 "gemm_x3: workspace too small");
   MSFNO_REQUIRE(bscale && batch <= 65535, MSFNO_EINVAL, "gemm_x3: bad arguments");
-  MSFNO_REQUIRE(!epi.addend && !epi.act && !epi.relu_period && !epi.rowscale && !epi.b_planes &&
+  MSFNO_REQUIRE(!epi.addend && !epi.act && !epi.relu_period && !epi.b_planes &&
                     !epi.c_planes && !epi.b2,
                 MSFNO_EUNSUPPORTED, "gemm_x3: bias-only epilogue");
   const int Mp = (int)round_up(M, 256), Kp = (int)round_up(K, 16);
@@ -574,19 +565,14 @@ int gemm_x3(const float* A, int lda, const float* bscale, const float* B, float*
   p.x3_bscale = bscale;
   p.x3_rowmul = rowmul;
   p.x3_ldrm = Mp;
-  // tiles as x6_tile (MSFNO_X6_TILE overrides: 6 = 256x256, 4 = 256x128, 0 = 128x128)
   const GemmTile tile = x6_tile(M, N, batch);
-  const int bm = (tile == TILE_256x256 || tile == TILE_256x128) ? 256 : 128;
-  const int bn = tile == TILE_256x256 ? 256 : 128;
+  const int bm = tile == TILE_256x256 ? 256 : 128, bn = bm;
   p.tiles_m = (int)cdiv(M, bm);
   p.tiles_n = (int)cdiv(N, bn);
   const dim3 grid(p.tiles_m * p.tiles_n, 1, batch);
   if (tile == TILE_256x256) {
     if (p.bias) launch_x3_e<256, 256, 4, 2, EPI_BIAS>(p, grid, s);
     else launch_x3_e<256, 256, 4, 2, 0>(p, grid, s);
-  } else if (tile == TILE_256x128) {
-    if (p.bias) launch_x3_e<256, 128, 4, 2, EPI_BIAS>(p, grid, s);
-    else launch_x3_e<256, 128, 4, 2, 0>(p, grid, s);
   } else {
     if (p.bias) launch_x3_e<128, 128, 2, 2, EPI_BIAS>(p, grid, s);
     else launch_x3_e<128, 128, 2, 2, 0>(p, grid, s);
@@ -594,15 +580,15 @@ int gemm_x3(const float* A, int lda, const float* bscale, const float* B, float*
   return launch_check("gemm_x3");
 }
 
-int gemm_dense(GemmRole role, GemmTile f32_tile, const float* A, const float* B, float* C, int M,
+int gemm_dense(GemmTile f32_tile, const float* A, const float* B, float* C, int M,
                int N, int K, int lda, int ldb, int ldc, int64_t sA, int64_t sB, int64_t sC,
                int batch, const GemmEpi& epi, void* ws, size_t ws_bytes, hipStream_t s) {
   MSFNO_REQUIRE(!(epi.b_planes || epi.c_planes) || (gemm_use_x6() && ws), MSFNO_EINVAL,
                 "gemm_dense: plane operands need the x6 engine");
-  if (gemm_use_x6() && ws && epi.act != 2 && !epi.rowscale)
+  if (gemm_use_x6() && ws && epi.act != 2)
     return gemm_x6(x6_tile(M, N, batch), A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC, batch, epi,
                    ws, ws_bytes, s);
-  return gemm_uniform(role_tile(role, f32_tile), A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC,
+  return gemm_uniform(f32_tile, A, B, C, M, N, K, lda, ldb, ldc, sA, sB, sC,
                       batch, epi, s);
 }
 

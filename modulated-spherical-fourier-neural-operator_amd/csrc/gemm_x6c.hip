@@ -10,11 +10,11 @@
 // Each product is an x6 product (gemm_x6p.hip) of bf16x3 planes, so both
 // operands carry a third "matrix": Ws = Wr + Wi (weight prep) and Xs = Xr + Xi,
 // which the producer of X writes next to Xr and Xi (the previous layer's
-// epilogue, or split3m for layer 0).  ComplexReLU(real) (activations.py:42-46)
+// epilogue; layer 0 forms it while it stages its fp32 input).  ComplexReLU(real) (activations.py:42-46)
 // is applied to Re in the epilogue, before Ys = Re + Im is formed.
 //
-// Activation layout ("3M planes"): X[b][mat][plane][c][ld], mat 0 = real,
-// 1 = imaginary, 2 = real + imaginary.
+// Activations ("3M planes"): matrices 0 = real, 1 = imaginary, 2 = real + imaginary, three
+// bf16 planes each, stored in the tiled layout described at X6CParams below.
 // Tile 128 complex rows x 128 columns x 16 (k), 8 waves as 4 (M) x 2 (N), each
 // wave 32 x 64 with three accumulator sets (P1, P2, P3).  Stage (72 KB) = A: 3
 // matrices x 3 planes x [128][16] + B: 3 x 3 x [16][128]; two stages, one k-tile
@@ -106,7 +106,7 @@ struct X6CParams {
   int64_t cs_b;
 };
 
-// Tiled 3M activations (LAY, MSFNO_X6C_TILED): the planes of a layer's activation
+// Tiled 3M activations (LAY): the planes of a layer's activation
 // stored as the LDS image of the next layer's B stages, [b][tn][kt][mat*3+plane][16
 // rows][128 columns, 8-column chunks XOR-swizzled by 4 (row & 3)]: one k-tile stage of
 // one column tile is a contiguous 36 KB, so the B DMA reads whole 1-KB pieces and the
@@ -210,95 +210,13 @@ __global__ void spec_weights_3m_kernel(SpecWeightsX6p a) {
   }
 }
 
-// S fp32 rows [b][ri][c] (ld ldS) -> 3M planes [b][mat][plane][c][ldx]
-// 8 columns per thread: 16-B loads of re and im, 16-B stores of the 9 planes
-// (ldS % 4 == 0, ldx % 8 == 0, 16-B aligned bases); the ragged row tail per column
-__global__ void split3m_x8_kernel(const float* __restrict__ S, unsigned short* __restrict__ X,
-                                  int C, int N, int ldS, int ldx, int64_t x_b, int64_t x_mat,
-                                  int64_t x_plane) {
-  const int b = blockIdx.y;
-  const int c8 = (N + 7) / 8;
-  const int64_t n = (int64_t)C * c8;
-  const float* Sb = S + (int64_t)b * 2 * C * ldS;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(e / c8), col = 8 * (int)(e - (int64_t)c * c8);
-    const float* re = Sb + (int64_t)c * ldS + col;
-    const float* im = Sb + (int64_t)(C + c) * ldS + col;
-    float r[8], i[8];
-    if (col + 8 <= N) {
-      const float4 r0 = *reinterpret_cast<const float4*>(re), r1 = *reinterpret_cast<const float4*>(re + 4);
-      const float4 i0 = *reinterpret_cast<const float4*>(im), i1 = *reinterpret_cast<const float4*>(im + 4);
-      r[0] = r0.x; r[1] = r0.y; r[2] = r0.z; r[3] = r0.w; r[4] = r1.x; r[5] = r1.y; r[6] = r1.z; r[7] = r1.w;
-      i[0] = i0.x; i[1] = i0.y; i[2] = i0.z; i[3] = i0.w; i[4] = i1.x; i[5] = i1.y; i[6] = i1.z; i[7] = i1.w;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        r[q] = col + q < N ? re[q] : 0.f;
-        i[q] = col + q < N ? im[q] : 0.f;
-      }
-    }
-    unsigned short* d = X + b * x_b + (int64_t)c * ldx + col;
-#pragma unroll
-    for (int mat = 0; mat < 3; ++mat) {
-      uint32_t t[3][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float a0 = mat == 0 ? r[2 * q] : (mat == 1 ? i[2 * q] : r[2 * q] + i[2 * q]);
-        const float a1 = mat == 0 ? r[2 * q + 1] : (mat == 1 ? i[2 * q + 1] : r[2 * q + 1] + i[2 * q + 1]);
-        split2(a0, a1, t[0][q], t[1][q], t[2][q]);
-      }
-      unsigned short* q0 = d + mat * x_mat;
-      // columns past N are written as the split of 0 (the planes' pad columns)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-        *reinterpret_cast<uint4*>(q0 + pl * x_plane) = make_uint4(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
-    }
-  }
-}
-
-__global__ void split3m_kernel(const float* __restrict__ S, unsigned short* __restrict__ X, int C,
-                               int N, int ldS, int ldx, int64_t x_b, int64_t x_mat,
-                               int64_t x_plane) {
-  const int b = blockIdx.y;
-  const int cp = (N + 1) / 2;
-  const int64_t n = (int64_t)C * cp;
-  const float* Sb = S + (int64_t)b * 2 * C * ldS;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(e / cp), col = 2 * (int)(e - (int64_t)c * cp);
-    const float* re = Sb + (int64_t)c * ldS + col;
-    const float* im = Sb + (int64_t)(C + c) * ldS + col;
-    const bool two = col + 1 < N;
-    const float r0 = re[0], r1 = two ? re[1] : 0.f;
-    const float i0 = im[0], i1 = two ? im[1] : 0.f;
-    const float v[3][2] = {{r0, r1}, {i0, i1}, {r0 + i0, r1 + i1}};
-    unsigned short* d = X + b * x_b + (int64_t)c * ldx + col;
-#pragma unroll
-    for (int mat = 0; mat < 3; ++mat) {
-      uint32_t t0, t1, t2;
-      split2(v[mat][0], v[mat][1], t0, t1, t2);
-      unsigned short* q = d + mat * x_mat;
-      if (two) {
-        *reinterpret_cast<uint32_t*>(q) = t0;
-        *reinterpret_cast<uint32_t*>(q + x_plane) = t1;
-        *reinterpret_cast<uint32_t*>(q + 2 * x_plane) = t2;
-      } else {
-        q[0] = (unsigned short)t0;
-        q[x_plane] = (unsigned short)t1;
-        q[2 * x_plane] = (unsigned short)t2;
-      }
-    }
-  }
-}
-
 // WGM x WGN waves: 4 x 2 (32 x 64 per wave, two waves per SIMD) or 2 x 2 (64 x 64
 // per wave, one wave per SIMD: a third fewer LDS fragment reads per MFMA)
 // BF32: the B operand arrives as fp32 Re / Im rows (layer 0, straight from the
 // forward Legendre GEMM): each thread loads a float4 of Re and of Im for the next
 // k-tile before the current one's MFMAs, and after them forms Re + Im, splits the
 // three into bf16x3 and writes the nine B planes into the LDS stage; only A is DMA'd
-// DBG (diagnostic timing builds only, wrong results; MSFNO_X6C_DBG): 1 no vmcnt wait
+// DBG (diagnostic timing builds, wrong results; none is instantiated): 1 no vmcnt wait
 // for the k-tile DMA, 2 no DMA in the loop at all (stale stages), 4 no MFMAs
 // LAY: bit 1 = B planes read in the tiled layout, bit 2 = planes written tiled
 // NS: LDS stages (2; 3 for the x3h DMA-fed layers: two k-tiles in flight, 144 KB)
@@ -612,7 +530,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
       q.sC = p.y_b;
       q.sCxp = p.y_plane;
       gemm_epilogue<BM, BN, EPI_PLANES, WGM, WGN, MT, NT, 32, floatx16, false>(
-          q, acc[mat], lds, nullptr, nullptr, nullptr, p.co, N, p.ldy, m0, n0, 0);
+          q, acc[mat], lds, nullptr, nullptr, nullptr, p.co, N, p.ldy, m0, n0);
       __syncthreads();
     }
   } else {
@@ -621,7 +539,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
       float* C = p.S + z * p.s_b + (mat ? p.s_im : 0);
       q.vecC = (p.ldS % 4 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
       gemm_epilogue<BM, BN, 0, WGM, WGN>(q, acc[mat], lds, nullptr, C, nullptr, p.co, N, p.ldS,
-                                         m0, n0, 0);
+                                         m0, n0);
       __syncthreads();
     }
   }
@@ -651,34 +569,14 @@ int launch_spec_weights_3m(const SpecWeightsX6p& a, hipStream_t s) {
   return launch_check("spec_weights_3m");
 }
 
-int launch_split3m(const float* S, unsigned short* X, int B, int C, int N, int ldS, int ldx,
-                   hipStream_t s) {
-  MSFNO_REQUIRE(ldx % 8 == 0, MSFNO_EINVAL, "split3m: ld must be a multiple of 8");
-  const int64_t x_plane = (int64_t)C * ldx;
-  if (ldS % 4 == 0 && ldx >= (N + 7) / 8 * 8 && ((reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(X)) & 15) == 0) {
-    const int64_t n8 = (int64_t)C * ((N + 7) / 8);
-    const int blocks = (int)std::min<int64_t>(cdiv(n8, 256), 4096);
-    hipLaunchKernelGGL(split3m_x8_kernel, dim3(blocks, B), dim3(256), 0, s, S, X, C, N, ldS, ldx,
-                       9 * x_plane, 3 * x_plane, x_plane);
-    return launch_check("split3m");
-  }
-  const int64_t n = (int64_t)C * ((N + 1) / 2);
-  const int blocks = (int)std::min<int64_t>(cdiv(n, 256), 2048);
-  hipLaunchKernelGGL(split3m_kernel, dim3(blocks, B), dim3(256), 0, s, S, X, C, N, ldS, ldx,
-                     9 * x_plane, 3 * x_plane, x_plane);
-  return launch_check("split3m");
-}
-
-// a layer on fp32 input rows (Re at Sin + b*2*ci*ldSin, Im ci rows later), split
-// while staged: out 3M planes Y (ld ldy) or fp32 rows [b][re/im][co] of Sout (ld ldSout)
+// layer 0 on fp32 input rows (Re at Sin + b*2*ci*ldSin, Im ci rows later), split while
+// staged: out 3M planes Y in the tiled layout
 int gemm_x6c_f32b(const unsigned short* Aw, int co, int ci, const float* Sin, int ldSin, int N,
-                  unsigned short* Y, int ldy, float* Sout, int ldSout, bool relu, int B,
-                  hipStream_t s, bool tiled_out) {
+                  unsigned short* Y, int ldy, bool relu, int B, hipStream_t s) {
   if (co <= 0 || N <= 0 || B <= 0) return MSFNO_OK;
   MSFNO_REQUIRE(ldSin % 4 == 0 && (reinterpret_cast<uintptr_t>(Sin) & 15) == 0 && ldSin >= N,
                 MSFNO_EINVAL, "gemm_x6c_f32b: fp32 rows need ld % 4 == 0 and 16-B alignment");
-  MSFNO_REQUIRE((Y != nullptr) != (Sout != nullptr), MSFNO_EINVAL, "gemm_x6c_f32b: one output");
-  MSFNO_REQUIRE(!Y || ldy % 8 == 0, MSFNO_EINVAL, "gemm_x6c_f32b: plane ld % 8 != 0");
+  MSFNO_REQUIRE(Y && ldy % 8 == 0, MSFNO_EINVAL, "gemm_x6c_f32b: plane output, ld % 8 == 0");
   X6CParams p{};
   p.Mp = (int)round_up(co, X6C_BM);
   const int KT = (int)cdiv(ci, X6C_BK);
@@ -695,23 +593,14 @@ int gemm_x6c_f32b(const unsigned short* Aw, int co, int ci, const float* Sin, in
   p.y_mat = 3 * p.y_plane;
   p.y_b = 3 * p.y_mat;
   p.ldy = ldy;
-  p.S = Sout;
-  p.s_b = 2LL * co * ldSout;
-  p.s_im = (int64_t)co * ldSout;
-  p.ldS = ldSout;
   p.co = co; p.ci = ci; p.N = N;
   p.tiles_m = p.Mp / X6C_BM;
   p.tiles_n = (int)cdiv(N, X6C_BN);
   p.relu = relu ? 1 : 0;
   const dim3 grid(p.tiles_m * p.tiles_n, 1, B);
-  if (Y && tiled_out) {
-    p.kt_out = p.Mp / 16;
-    p.y_b = x6c_tiled_elems(co, N);
-    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, true, 0, 2>), grid, dim3(512), 0, s, p);
-  } else if (Y)
-    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, true>), grid, dim3(512), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, true>), grid, dim3(512), 0, s, p);
+  p.kt_out = p.Mp / 16;
+  p.y_b = x6c_tiled_elems(co, N);
+  hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, true, 0, 2>), grid, dim3(512), 0, s, p);
   return launch_check("gemm_x6c_f32b");
 }
 
@@ -720,10 +609,10 @@ int64_t x6c_tiled_elems(int rows, int N) {
   return cdiv(N, X6C_BN) * round_up(rows, X6C_BM) * 9 * X6C_BN;
 }
 
-// one spectral-MLP layer: X (3M planes, ci rows, ld ldx) -> Y (3M planes, co rows,
-// ld ldx; relu) or, with S given, fp32 rows [b][re/im][co] of S (ld ldS)
+// one spectral-MLP layer on tiled 3M planes X (ci rows) -> tiled planes Y (co rows; relu)
+// or, with S given, fp32 rows [b][re/im][co] of S (ld ldS)
 int gemm_x6c(const unsigned short* Aw, int co, int ci, const unsigned short* X, int N, int ldx,
-             unsigned short* Y, float* S, int ldS, bool relu, int B, hipStream_t s, int lay) {
+             unsigned short* Y, float* S, int ldS, bool relu, int B, hipStream_t s) {
   if (co <= 0 || N <= 0 || B <= 0) return MSFNO_OK;
   MSFNO_REQUIRE(ldx % 8 == 0 && ldx >= 8 && (reinterpret_cast<uintptr_t>(X) & 15) == 0,
                 MSFNO_EINVAL, "gemm_x6c: X planes need ld % 8 == 0 and 16-B alignment");
@@ -737,7 +626,7 @@ int gemm_x6c(const unsigned short* Aw, int co, int ci, const unsigned short* X, 
   p.X = X;
   p.x_plane = (int64_t)ci * ldx;
   p.x_mat = 3 * p.x_plane;
-  p.x_b = 3 * p.x_mat;
+  p.x_b = x6c_tiled_elems(ci, N);
   p.ldx = ldx;
   p.Y = Y;
   p.y_plane = (int64_t)co * ldx;
@@ -753,57 +642,13 @@ int gemm_x6c(const unsigned short* Aw, int co, int ci, const unsigned short* X, 
   p.tiles_n = (int)cdiv(N, X6C_BN);
   p.relu = relu ? 1 : 0;
   const dim3 grid(p.tiles_m * p.tiles_n, 1, B);
-  if (lay) {  // tiled activations (input must be tiled: the hidden layers / output layer)
-    MSFNO_REQUIRE((lay & 1) != 0 && ((lay & 2) == 0 || Y), MSFNO_EINVAL, "gemm_x6c: tiled layout");
-    p.x_b = x6c_tiled_elems(ci, N);
-    p.kt_in = (int)round_up(ci, X6C_BM) / 16;
-    p.kt_out = p.Mp / 16;
-    if (Y) p.y_b = x6c_tiled_elems(co, N);
-    if (Y)
-      hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, false, 0, 3>), grid, dim3(512), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, false, 0, 1>), grid, dim3(512), 0, s, p);
-    return launch_check("gemm_x6c");
-  }
-  // MSFNO_X6C_WAVES: 8 (4 x 2 waves of 32 x 64), 24 (2 x 4 waves of 64 x 32: the same
-  // fragment bytes in 20 % fewer LDS read instructions), 4 (2 x 2 waves of 64 x 64)
-  static const int waves = [] {
-    const char* e = getenv("MSFNO_X6C_WAVES");
-    const int v = e ? atoi(e) : 8;
-    return (v == 4 || v == 24) ? v : 8;
-  }();
-  if (waves == 24) {
-    if (Y)
-      hipLaunchKernelGGL((gemm_x6c_kernel<true, 2, 4>), grid, dim3(512), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_x6c_kernel<false, 2, 4>), grid, dim3(512), 0, s, p);
-  } else if (waves == 4) {
-    if (Y)
-      hipLaunchKernelGGL((gemm_x6c_kernel<true, 2, 2>), grid, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_x6c_kernel<false, 2, 2>), grid, dim3(256), 0, s, p);
+  p.kt_in = (int)round_up(ci, X6C_BM) / 16;
+  p.kt_out = p.Mp / 16;
+  if (Y) {
+    p.y_b = x6c_tiled_elems(co, N);
+    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, false, 0, 3>), grid, dim3(512), 0, s, p);
   } else {
-    static const int dbg = [] {
-      const char* e = getenv("MSFNO_X6C_DBG");
-      return e ? atoi(e) : 0;
-    }();
-    if (dbg > 0 && dbg < 8) {
-      static void (*const kp[8])(X6CParams) = {
-          nullptr, gemm_x6c_kernel<true, 4, 2, false, 1>, gemm_x6c_kernel<true, 4, 2, false, 2>,
-          gemm_x6c_kernel<true, 4, 2, false, 3>, gemm_x6c_kernel<true, 4, 2, false, 4>,
-          gemm_x6c_kernel<true, 4, 2, false, 5>, gemm_x6c_kernel<true, 4, 2, false, 6>,
-          gemm_x6c_kernel<true, 4, 2, false, 7>};
-      static void (*const kf[8])(X6CParams) = {
-          nullptr, gemm_x6c_kernel<false, 4, 2, false, 1>, gemm_x6c_kernel<false, 4, 2, false, 2>,
-          gemm_x6c_kernel<false, 4, 2, false, 3>, gemm_x6c_kernel<false, 4, 2, false, 4>,
-          gemm_x6c_kernel<false, 4, 2, false, 5>, gemm_x6c_kernel<false, 4, 2, false, 6>,
-          gemm_x6c_kernel<false, 4, 2, false, 7>};
-      hipLaunchKernelGGL((Y ? kp[dbg] : kf[dbg]), grid, dim3(512), 0, s, p);
-    } else if (Y) {
-      hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2>), grid, dim3(512), 0, s, p);
-    } else {
-      hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2>), grid, dim3(512), 0, s, p);
-    }
+    hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, false, 0, 1>), grid, dim3(512), 0, s, p);
   }
   return launch_check("gemm_x6c");
 }
@@ -926,12 +771,7 @@ int gemm_x3c(const unsigned short* Aw, int co, int ci, const float* Sin, int ldS
   p.cs_b = cs_b;
   const dim3 grid(p.tiles_m * p.tiles_n, 1, B);
   // three LDS stages for the DMA-fed layers (two k-tiles in flight): layers 1/2
-  // 0.51 -> 0.49 ms, output 0.31 -> 0.29 ms (two interleaved pairs); MSFNO_X3C_NS=2
-  // keeps two (A/B)
-  static const int ns = [] {
-    const char* e = getenv("MSFNO_X3C_NS");
-    return (e && e[0] == '2') ? 2 : 3;
-  }();
+  // 0.51 -> 0.49 ms, output 0.31 -> 0.29 ms against two stages (two interleaved pairs)
   // grids that would not fill the chip twice (the network's 120 x 240 blocks: 57 column
   // tiles) take 64-row tiles of four waves, two stages, two workgroups per CU
   // (MSFNO_X3C_BM64=0 keeps the 128-row tiles; 2 takes 64 rows for every DMA-fed layer:
@@ -967,14 +807,10 @@ int gemm_x3c(const unsigned short* Aw, int co, int ci, const float* Sin, int ldS
   }
   if (Sin)
     hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, true, 0, 2, 2>), grid, dim3(512), 0, s, p);
-  else if (Y && ns == 3)
-    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, false, 0, 3, 2, 3>), grid, dim3(512), 0, s, p);
   else if (Y)
-    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, false, 0, 3, 2>), grid, dim3(512), 0, s, p);
-  else if (ns == 3)
-    hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, false, 0, 1, 2, 3>), grid, dim3(512), 0, s, p);
+    hipLaunchKernelGGL((gemm_x6c_kernel<true, 4, 2, false, 0, 3, 2, 3>), grid, dim3(512), 0, s, p);
   else
-    hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, false, 0, 1, 2>), grid, dim3(512), 0, s, p);
+    hipLaunchKernelGGL((gemm_x6c_kernel<false, 4, 2, false, 0, 1, 2, 3>), grid, dim3(512), 0, s, p);
   return launch_check("gemm_x3c");
 }
 

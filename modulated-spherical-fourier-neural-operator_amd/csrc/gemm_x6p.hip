@@ -314,7 +314,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_x6p_kernel(GemmParams p) {
   }
   __syncthreads();  // all DMA retired (vmcnt(0) above); the ring is free for the epilogue
   gemm_epilogue<BM, BN, EPI, WGM, WGN>(p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C,
-                                       addend, M, N, ldc, m0, n0, 0);
+                                       addend, M, N, ldc, m0, n0);
 }
 
 
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(GemmParams p) {
   }
   __syncthreads();
   gemm_epilogue<BM, BN, EPI, WGM, WGN, MT, NT, 16, floatx4q>(
-      p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C, addend, M, N, ldc, m0, n0, 0);
+      p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C, addend, M, N, ldc, m0, n0);
 }
 
 // ---- host ---------------------------------------------------------------------
@@ -487,19 +487,6 @@ size_t gemm_x6p_workspace(int M, int K, int batch_a) {
   // k padded to 32: covers the 16-deep (x6p) and 32-deep (x6q) A images
   const int64_t Mp = round_up(M, X6P_BM), Kp = round_up(K, 32);
   return (size_t)round_up(3 * Mp * Kp * 2 * (int64_t)batch_a, 256);
-}
-
-int gemm_x6p_split_a(const float* A, int M, int K, int lda, int64_t sA, int batch, void* ws,
-                     size_t ws_bytes, hipStream_t s) {
-  const int abatch = sA == 0 ? 1 : batch;
-  const int Mp = (int)round_up(M, X6P_BM), KT = (int)cdiv(K, X6P_BK);
-  MSFNO_REQUIRE(ws && ws_bytes >= gemm_x6p_workspace(M, K, abatch), MSFNO_EINVAL,
-                "gemm_x6p_split_a: workspace too small");
-  const int64_t pairs = (int64_t)Mp * KT * X6P_BK / 2;
-  const int blocks = (int)std::min<int64_t>(cdiv(pairs, 256), 1024);
-  hipLaunchKernelGGL(split_a_tiles_kernel<X6P_BK>, dim3(blocks, abatch), dim3(256), 0, s, A,
-                     static_cast<unsigned short*>(ws), M, K, lda, sA, Mp, KT);
-  return launch_check("split_a_tiles");
 }
 
 int launch_spec_weights_x6p(const SpecWeightsX6p& a, hipStream_t s) {
@@ -584,14 +571,13 @@ int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, in
   const size_t need = (size_t)round_up(3 * round_up(M, X6P_BM) * round_up(K, TKd) * 2 * (int64_t)abatch, 256);
   MSFNO_REQUIRE(epi.a_planes || (ws && ws_bytes >= need), MSFNO_EINVAL,
                 "gemm_x6p: workspace too small");
-  // a batched pre-split A (sA != 0) has gemm_x6p_split_a's layout: batch stride 3 planes
+  // a batched A image (sA != 0) has batch stride 3 planes
   MSFNO_REQUIRE(epi.b_planes, MSFNO_EINVAL, "gemm_x6p: B must be in the plane format");
   MSFNO_REQUIRE(batch <= 65535 && K > 0, MSFNO_EINVAL, "gemm_x6p: bad batch / K");
   MSFNO_REQUIRE(ldb % 8 == 0 && ldb >= 8 && sB % 8 == 0 && epi.b_plane_stride % 8 == 0 &&
                     (reinterpret_cast<uintptr_t>(epi.b_planes) & 15) == 0,
                 MSFNO_EINVAL, "gemm_x6p: B planes need ld, strides % 8 == 0 and 16-B alignment");
-  MSFNO_REQUIRE(epi.act != 2 && !epi.rowscale, MSFNO_EUNSUPPORTED,
-                "gemm_x6p: unsupported epilogue");
+  MSFNO_REQUIRE(epi.act != 2, MSFNO_EUNSUPPORTED, "gemm_x6p: unsupported epilogue");
   const int Mp = (int)round_up(M, X6P_BM), KT = (int)cdiv(K, TKd);
   unsigned short* Ax = static_cast<unsigned short*>(ws);
   if (epi.a_planes) {

@@ -28,17 +28,6 @@ struct C2RPlanes {
 bool fft_c2r_planes_supported(const FFTPlan& f, int mmax);
 bool fft_r2c_planes_supported(const FFTPlan& f, int mmax);
 
-// fused FFT + transpose (block path); only for plans with a compiled codelet
-bool fft_tile_supported(const FFTPlan& f);
-// x (B*C, nlat, N) -> Xt (mmax, R=2BC, ldk) raw spectrum·scale (+ per-row (mean, M2))
-int launch_fft_r2c_tile(const FFTPlan& f, const float* x, float* Xt, float2* rowstats, int B,
-                        int C, int nlat, int mmax, int ldk, float scale, hipStream_t s);
-// Yt (mmax, R, ldk) -> out (B*C, nlat, N), GELU if act, optional output row stats
-int launch_fft_c2r_tile(const FFTPlan& f, const float* Yt, float* out, float2* rowstats, int B,
-                        int C, int nlat, int mmax, int mact, int ldk, int act, hipStream_t s);
-// m = 0 slice of Xt: v -> scale[bc]·v + 2π·shift[bc] (real rows), scale[bc]·v (imag rows)
-int launch_dc_fixup(float* Xt, int B, int C, int nlat, int ldk, const float* nscale,
-                    const float* nshift, hipStream_t s);
 
 // ---- spectral.hip ------------------------------------------------------------
 // Xn (BC, nlat, mmax) complex -> Xt (mmax, R=2BC, ldk); per-bc affine of the
@@ -144,9 +133,9 @@ int launch_mlp_fused_h(const float* x1, const float* scale, const float* shift,
 int launch_split_complex_weight(const float* w, float* Ar, float* Ai, int Ci, int Co,
                                 hipStream_t s);
 // Y = W.X complex per column (3M scheme), X/Y rows [b][re|im][ci|co] in the S layout;
-// relu: ComplexReLU(real) on the output; tile 0: 128x64, 1: 64x128, 2: 128x128
+// relu: ComplexReLU(real) on the output
 int gemm_c3m(const float* Ar, const float* Ai, const float* X, float* Y, int co, int ci, int N,
-             int ldx, int ldy, int64_t sX, int64_t sY, int B, bool relu, int tile, hipStream_t s);
+             int ldx, int ldy, int64_t sX, int64_t sY, int B, bool relu, hipStream_t s);
 // complex (Ci,Co,2) weight -> real (2Co x 2Ci) block matrix [[Wr^T,-Wi^T],[Wi^T,Wr^T]]
 int launch_expand_complex_weight(const float* w, float* Wexp, int Ci, int Co, hipStream_t s);
 // (mmax,lmax,nlat) reference table -> plan GEMM layout (general or symmetric)

@@ -123,10 +123,10 @@ constexpr int WGM = 2, WGN = 2, WM = BM / WGM, MT = WM / 32;
 
 __device__ __forceinline__ int swz(int row) { return (row >> 3) & 1; }
 
-// BN: 64 or 192 columns per tile (192: one tile spans a whole problem's N <= 184 — A
-// is read once, not once per 64 columns); PF: k-tiles in flight in registers (1, 2)
-// DBG (diagnostic timing builds, wrong results; MSFNO_LEG_X3_DBG): 1 no MFMAs, 4 no
-// main-loop loads (stale registers)
+// BN: columns per tile; PF: k-tiles in flight in registers; DBG: diagnostic timing
+// builds with wrong results (1 no MFMAs, 4 no main-loop loads).  Only <64, 1> is
+// instantiated: 128 / 192 columns, PF = 2 and the diagnostic builds measured no faster
+// 
 //
 // Row scales per k-tile: the 8 threads that stage one row's 32 k of a k-tile reduce
 // their max by lane shuffles and split the row under sigma = 2^(15 - e) of it; the
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
   q.segC_w = p.segC_w;
   q.segC_stride = p.segC_stride;
   gemm_epilogue<BM, BN, 0, WGM, WGN>(q, acc, reinterpret_cast<float*>(lds_raw), nullptr,
-                                     p.C + d.offC, nullptr, M, N, d.ldc, m0, n0, 0);
+                                     p.C + d.offC, nullptr, M, N, d.ldc, m0, n0);
 }
 
 // ---- register-resident A (the inverse problems, K <= X3R_KMAX) -------------------------
@@ -367,8 +367,15 @@ constexpr int X3R_NSTG = 3;
 constexpr int X3R_STAGE = 2 * (X3R_KMAX / 16) * 1024;  // bytes per stage (max Kp)
 
 // masked lanes store here, so every wave issues exactly 16 stores per chunk (the
-// DMA waits count them)
-__device__ float x3r_sink[256];
+// DMA waits count them).  One 256-B slot per workgroup (modulo X3R_SINKS): with a single
+// slot every workgroup of the chip stored to the same lines, and the kernels' time
+// depended on the address the linker gave them (legendre_x3f 22.0 to 34.8 us per launch
+// in the network step over three placements)
+constexpr int X3R_SINKS = 64;
+__device__ float x3r_sink[X3R_SINKS * 64];
+__device__ __forceinline__ float* x3r_sink_slot(int lane) {
+  return x3r_sink + (blockIdx.x % X3R_SINKS) * 64 + lane;  // lane < 64
+}
 
 __device__ __forceinline__ int x3r_swz(int n) { return (n >> 3) & 1; }
 
@@ -487,7 +494,7 @@ __device__ __forceinline__ void x3r_body(const X3DParams& p, const GemmDesc& d, 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int rr = rbase + (r & 3) + 8 * (r >> 2);
-      float* dst = (rr < M && col < N) ? Cb + (int64_t)rr * d.ldc + cc : x3r_sink + lane;
+      float* dst = (rr < M && col < N) ? Cb + (int64_t)rr * d.ldc + cc : x3r_sink_slot(lane);
       *dst = acc[r] * isv[r] * it;
     }
   }
@@ -610,7 +617,7 @@ __device__ __forceinline__ void x3f_body(const X3FParams& p, const GemmDesc& d, 
     for (int e = 0; e < 4; ++e) {
       const int rl = 16 * j + 4 * ra + e;  // row within the workgroup's block
       const bool ok = rl < rows && col < N;
-      float* dst = ok ? Cb + (int64_t)(m0 + rl) * d.ldc + col : x3r_sink + lane;
+      float* dst = ok ? Cb + (int64_t)(m0 + rl) * d.ldc + col : x3r_sink_slot(lane);
       *dst = acc[e] * isr_s[min(rl, X3F_RB - 1)] * it;
     }
   }
@@ -669,7 +676,7 @@ int legendre_x3r(const float* A, const unsigned short* img, const float* invs, f
   if (ndesc <= 0 || tiles <= 0) return MSFNO_OK;
   MSFNO_REQUIRE(A && img && invs && C && descs && tile_desc, MSFNO_EINVAL,
                 "legendre_x3r: null operand");
-  MSFNO_REQUIRE(!e.rowscale && !e.bias && !e.addend && !e.segA_w, MSFNO_EUNSUPPORTED,
+  MSFNO_REQUIRE(!e.bias && !e.addend && !e.segA_w, MSFNO_EUNSUPPORTED,
                 "legendre_x3r: plain epilogue, unsegmented A only");
   X3DParams p{};
   p.A = A; p.img = img; p.invs = invs; p.C = C;
@@ -686,30 +693,12 @@ int launch_legendre_x3_image(const float* table, const GemmDesc* descs, int ndes
   return launch_check("legendre_x3_image");
 }
 
-// tile width of the x3h Legendre problems (MSFNO_LEG_X3_BN=64|128|192, per direction:
-// MSFNO_LEG_X3_BN=<forward>,<inverse>)
-int x3d_bn(int inverse) {
-  static int bn[2] = {0, 0};
-  if (!bn[0]) {
-    bn[0] = bn[1] = 64;
-    if (const char* e = getenv("MSFNO_LEG_X3_BN")) {
-      int a = 0, b = 0;
-      const int n = sscanf(e, "%d,%d", &a, &b);
-      if (n >= 1) bn[0] = bn[1] = a;
-      if (n == 2) bn[1] = b;
-    }
-    for (int& v : bn)
-      if (v != 128 && v != 192) v = 64;
-  }
-  return bn[inverse ? 1 : 0];
-}
-
 int legendre_x3(const float* A, const unsigned short* img, const float* invs, float* C,
-                const GemmDesc* descs, const int* tile_desc, int ndesc, int tiles, int bn,
+                const GemmDesc* descs, const int* tile_desc, int ndesc, int tiles,
                 const GemmEpi& e, hipStream_t s) {
   if (ndesc <= 0 || tiles <= 0) return MSFNO_OK;
   MSFNO_REQUIRE(A && img && invs && C && descs, MSFNO_EINVAL, "legendre_x3: null operand");
-  MSFNO_REQUIRE(!e.rowscale && !e.bias && !e.addend, MSFNO_EUNSUPPORTED,
+  MSFNO_REQUIRE(!e.bias && !e.addend, MSFNO_EUNSUPPORTED,
                 "legendre_x3: plain epilogue only");
   X3DParams p{};
   p.A = A; p.img = img; p.invs = invs; p.C = C;
@@ -717,29 +706,8 @@ int legendre_x3(const float* A, const unsigned short* img, const float* invs, fl
   p.segA_w = e.segA_w; p.segA_stride = e.segA_stride;
   p.segC_w = e.segC_w; p.segC_stride = e.segC_stride;
   p.vecC = (reinterpret_cast<uintptr_t>(C) & 15) == 0;  // every ldc / offC is a multiple of 4
-  static const int pf = [] {  // k-tiles of register prefetch (2 measured no faster)
-    const char* e = getenv("MSFNO_LEG_X3_PF");
-    return (e && e[0] == '2') ? 2 : 1;
-  }();
-  static const int dbg = [] {
-    const char* e = getenv("MSFNO_LEG_X3_DBG");
-    return e ? atoi(e) & 7 : 0;
-  }();
-  static void (*const kd[8])(X3DParams) = {
-      legendre_x3_kernel<64, 2, 0>, legendre_x3_kernel<64, 2, 1>, legendre_x3_kernel<64, 2, 0>,
-      legendre_x3_kernel<64, 2, 1>, legendre_x3_kernel<64, 2, 4>, legendre_x3_kernel<64, 2, 5>,
-      legendre_x3_kernel<64, 2, 4>, legendre_x3_kernel<64, 2, 5>};
-  if (dbg)
-    hipLaunchKernelGGL(kd[dbg], dim3(tiles), dim3(256), 0, s, p);
-  else if (bn == 64)
-    hipLaunchKernelGGL((pf == 1 ? legendre_x3_kernel<64, 1> : legendre_x3_kernel<64, 2>), dim3(tiles),
-                       dim3(256), 0, s, p);
-  else if (bn == 128)
-    hipLaunchKernelGGL((pf == 1 ? legendre_x3_kernel<128, 1> : legendre_x3_kernel<128, 2>),
-                       dim3(tiles), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((pf == 1 ? legendre_x3_kernel<192, 1> : legendre_x3_kernel<192, 2>),
-                       dim3(tiles), dim3(256), 0, s, p);
+  // X3D_BN-column tiles, one k-tile of register prefetch (two measured no faster)
+  hipLaunchKernelGGL((legendre_x3_kernel<X3D_BN, 1>), dim3(tiles), dim3(256), 0, s, p);
   return launch_check("legendre_x3");
 }
 

@@ -70,7 +70,6 @@ struct MlpFusedParams {
   const float* b2;      // [C] or null
   int64_t P;
   int tiles_per_field;
-  unsigned long long* stamps;  // diagnostic build only (STAMP): [workgroup][8] s_memtime
 };
 
 // physical 16-B half of logical k-half h in an A-image row m (conflict-free
@@ -158,20 +157,8 @@ __device__ __forceinline__ const unsigned short* mf_slice_src(const MlpFusedPara
 template <int SCHED, int STAMP, int DBG = 0, int MF_AHEAD = 2, int XS = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void mlp_fused_kernel(MlpFusedParams p) {
-  // DBG (diagnostic timing builds only, wrong results): 1 no ring waits / barriers /
-  // refills in the steps, 2 no MFMAs, 4 no GELU / split of the hidden blocks, 8 the
-  // A fragments of every k-step re-use the first k-step's (no ds_reads in the loop)
-  // diagnostic phase clock (MSFNO_MF_STAMPS=1; never in the product launch): wave 0 of
-  // each workgroup records s_memtime at phase boundaries and the cycles it spent in
-  // the ring waits + barriers
-  unsigned long long st_wait = 0;
-  auto stamp = [&](int k, unsigned long long v) {
-    if constexpr (STAMP) {
-      if (threadIdx.x == 0) p.stamps[(int64_t)blockIdx.x * 8 + k] = v;
-    }
-  };
-  if constexpr (STAMP) stamp(0, __builtin_amdgcn_s_memtime());
-  const unsigned long long rt0 = STAMP ? __builtin_amdgcn_s_memrealtime() : 0;
+  // STAMP, DBG, XS: template parameters of retired diagnostic / A/B builds (a phase clock,
+  // timing builds with wrong results, cross-step prefetch); only <.., 0, 0, .., 0> is built
   // LDS: ring slots [0, 96K); x1 staging [24K, 152K) at the tile start (only slot 0
   // is live then); two 16-KB residual chunks [96K, 128K) during the steps; vectors at
   // the top
@@ -229,7 +216,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (STAMP) stamp(1, __builtin_amdgcn_s_memtime());
 
   // ---- x1 -> normalised bf16x3 B fragments: k-step ks holds channels 16 ks + 8 half + 0..7
   bf16x8 xf[16][3];
@@ -268,7 +254,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   __syncthreads();  // the staging area is free: slices 1, 2 may land in it
   issue(1);
   issue(2);
-  if constexpr (STAMP) stamp(2, __builtin_amdgcn_s_memtime());
   floatx16 hacc[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -282,9 +267,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   // right after the barrier and the DMA issue runs under the MFMAs
   // extra: residual-chunk DMA instructions this wave issued after slice q (below)
   auto step_begin = [&](int q, int extra = 0) {
-    if constexpr ((DBG & 1) != 0) return ring + (q % MF_NS) * MF_SLICE_ELEMS;
-    unsigned long long w0 = 0;
-    if constexpr (STAMP) w0 = __builtin_amdgcn_s_memtime();
     const int after = min(2, MF_NSLICE - 1 - q);  // slices issued after q
     if (after >= 2 && extra)
       asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
@@ -296,15 +278,10 @@ void mlp_fused_kernel(MlpFusedParams p) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if constexpr (STAMP) st_wait += __builtin_amdgcn_s_memtime() - w0;
     return ring + (q % MF_NS) * MF_SLICE_ELEMS;
   };
 
   auto mfma6 = [](const bf16x8 (&a)[3], const bf16x8 (&b)[3], floatx16 c) {
-    if constexpr ((DBG & 2) != 0) {
-      c[0] += (float)a[0][0] + (float)b[0][0];  // keep the operands live, no MFMA
-      return c;
-    }
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
@@ -337,10 +314,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   auto conv_pair = [&](int j, int e2, auto par_c) {
     constexpr int PAR = decltype(par_c)::value;
     uint32_t (&h)[2][3][4] = hfu;
-    if constexpr ((DBG & 4) != 0) {
-      h[e2 >> 2][0][e2 & 3] = __float_as_uint(hacc[PAR][2 * e2]);
-      return;
-    }
     const int r = 2 * e2;
     const float2 b = *reinterpret_cast<const float2*>(b1s + 32 * j + (r >> 2) * 8 + 4 * half + (r & 3));
     f32x2 v = {hacc[PAR][r] + b.x, hacc[PAR][r + 1] + b.y};
@@ -351,7 +324,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   // fc1 slice W1(j, KH) into hacc[PAR]; CONV: pairs 4 KH .. 4 KH + 3 of block jc
   // (in hacc[PAR ^ 1]) are converted under its MFMAs, one per odd k-step
   auto refill = [&](int q) {
-    if constexpr ((DBG & 1) != 0) return;
     if (q + 3 < MF_NSLICE) issue(q + 3);
   };
   auto fc1_step = [&](const unsigned short* slot, int q, auto kh_c, auto par_c, auto conv_c,
@@ -367,13 +339,13 @@ void mlp_fused_kernel(MlpFusedParams p) {
         a[k][pl] = *reinterpret_cast<const bf16x8*>(slot + (pl * 8 + k) * 512 + a_lane);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-      if (ks + MF_AHEAD < 8 && (DBG & 8) == 0) {
+      if (ks + MF_AHEAD < 8) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
           a[(ks + MF_AHEAD) % (MF_AHEAD + 1)][pl] =
               *reinterpret_cast<const bf16x8*>(slot + (pl * 8 + ks + MF_AHEAD) * 512 + a_lane);
       }
-      hacc[PAR] = mfma6(a[(DBG & 8) ? 0 : ks % (MF_AHEAD + 1)], xf[KH * 8 + ks], hacc[PAR]);
+      hacc[PAR] = mfma6(a[ks % (MF_AHEAD + 1)], xf[KH * 8 + ks], hacc[PAR]);
       if (ks == 0) refill(q);
       if constexpr (CONV) {
         if (ks & 1) conv_pair(jc, 4 * KH + (ks >> 1), PPrev{});
@@ -398,7 +370,7 @@ void mlp_fused_kernel(MlpFusedParams p) {
       for (int pl = 0; pl < 3; ++pl) a[k][pl] = *reinterpret_cast<const bf16x8*>(slot + aoff(k, pl));
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
-      if (it + MF_AHEAD < 8 && (DBG & 8) == 0) {
+      if (it + MF_AHEAD < 8) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
           a[(it + MF_AHEAD) % (MF_AHEAD + 1)][pl] =
@@ -410,7 +382,7 @@ void mlp_fused_kernel(MlpFusedParams p) {
                             mf_frag(h[s][1][0], h[s][1][1], h[s][1][2], h[s][1][3]),
                             mf_frag(h[s][2][0], h[s][2][1], h[s][2][2], h[s][2][3])};
       oacc[OH * 4 + (it >> 1)] =
-          mfma6(a[(DBG & 8) ? 0 : it % (MF_AHEAD + 1)], hb, oacc[OH * 4 + (it >> 1)]);
+          mfma6(a[it % (MF_AHEAD + 1)], hb, oacc[OH * 4 + (it >> 1)]);
       if (it == 0) refill(q);
       kstep_schedule(it + MF_AHEAD < 8);
     }
@@ -486,9 +458,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
     // slice q visible to every wave; DMA instructions this wave issued after slice q:
     // slices q + 1, q + 2 (6 each) and, around the residual issues, 12 more
     auto slice_wait = [&](int q) {
-      if constexpr ((DBG & 1) != 0) return;
-      unsigned long long w0 = 0;
-      if constexpr (STAMP) w0 = __builtin_amdgcn_s_memtime();
       const int after = min(2, MF_NSLICE - 1 - q);
       const bool ex = has_res && ((q >= QA + 2 && q <= QA + 4) || (q >= QB + 2 && q <= QB + 3));
       if (after >= 2 && ex)
@@ -501,7 +470,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if constexpr (STAMP) st_wait += __builtin_amdgcn_s_memtime() - w0;
     };
     // step q: a W1 slice (KIND 0: hidden block into hacc[PAR], converting block jc of
     // hacc[PAR ^ 1] under it when CONV) or a W2 slice (KIND 1: out rows 128 SUB ..)
@@ -513,8 +481,8 @@ void mlp_fused_kernel(MlpFusedParams p) {
       using PPrev = std::integral_constant<int, PAR ^ 1>;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) {
-        if (ks + 2 < 8 && (DBG & 8) == 0) load_frag(q, kind_c, ks + 2);
-        const int fi = (DBG & 8) ? 0 : (ks & 3);
+        if (ks + 2 < 8) load_frag(q, kind_c, ks + 2);
+        const int fi = ks & 3;
         if constexpr (KIND == 0) {
           hacc[PAR] = mfma6(af[fi], xf[SUB * 8 + ks], hacc[PAR]);
           if constexpr (CONV) {
@@ -528,13 +496,13 @@ void mlp_fused_kernel(MlpFusedParams p) {
                                 mf_frag(h[sh][2][0], h[sh][2][1], h[sh][2][2], h[sh][2][3])};
           oacc[SUB * 4 + (ks >> 1)] = mfma6(af[fi], hb, oacc[SUB * 4 + (ks >> 1)]);
         }
-        kstep_schedule(ks + 2 < 8 && (DBG & 8) == 0);
+        kstep_schedule(ks + 2 < 8);
         if constexpr (NEXT != 2) {
           if (ks == 6) {
             slice_wait(q + 1);
             refill(q + 1);
           }
-          if (ks >= 6 && (DBG & 8) == 0)
+          if (ks >= 6)
             load_frag(q + 1, std::integral_constant<int, NEXT>{}, ks - 6);
         }
       }
@@ -652,7 +620,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   }
   }  // XS
 
-  if constexpr (STAMP) stamp(3, __builtin_amdgcn_s_memtime());
   // ---- store (all DMA retired: the last step waited vmcnt(0)) ------------------------
   if (valid) {
     float* o = p.out + (int64_t)z * MF_C * P + px;
@@ -661,62 +628,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) o[(int64_t)(32 * ob + (r >> 2) * 8 + 4 * half + (r & 3)) * P] = oacc[ob][r];
   }
-  if constexpr (STAMP) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(4, __builtin_amdgcn_s_memtime());
-    stamp(5, st_wait);
-    stamp(6, (unsigned long long)__smid());
-    stamp(7, __builtin_amdgcn_s_memrealtime() - rt0);
-  }
-}
-
-// diagnostic launch (MSFNO_MF_STAMPS=1): synchronises, prints the median cycles of
-// each phase over the workgroups to stderr
-int mlp_fused_stamped(MlpFusedParams p, int64_t tiles, int sched, hipStream_t s) {
-  std::vector<unsigned long long> h((size_t)tiles * 8);
-  unsigned long long* d = nullptr;
-  MSFNO_CHECK_HIP(hipMalloc(&d, h.size() * 8));
-  p.stamps = d;
-  static const int dbg = [] {
-    const char* e = getenv("MSFNO_MF_DBG");
-    return e ? atoi(e) : 0;
-  }();
-  if (dbg == 1)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 1>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else if (dbg == 2)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 2>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else if (dbg == 4)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 4>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else if (dbg == 8)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 8>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else if (dbg == 13)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1, 13>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-
-  else if (sched)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 1>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((mlp_fused_kernel<0, 1>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  MSFNO_CHECK_HIP(hipStreamSynchronize(s));
-  MSFNO_CHECK_HIP(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-  MSFNO_CHECK_HIP(hipFree(d));
-  auto med = [&](auto f) {
-    std::vector<double> v;
-    for (int64_t t = 0; t < tiles; ++t) v.push_back(f(&h[(size_t)t * 8]));
-    std::sort(v.begin(), v.end());
-    return v[v.size() / 2];
-  };
-  std::fprintf(stderr,
-               "mlp_fused stamps (median cycles over %lld workgroups): prologue-load %.0f, "
-               "split %.0f, steps %.0f (of which ring waits %.0f), store %.0f, total %.0f "
-               "(%.2f us at 100 MHz realtime)\n",
-               (long long)tiles, med([](auto* x) { return (double)(x[1] - x[0]); }),
-               med([](auto* x) { return (double)(x[2] - x[1]); }),
-               med([](auto* x) { return (double)(x[3] - x[2]); }),
-               med([](auto* x) { return (double)x[5]; }),
-               med([](auto* x) { return (double)(x[4] - x[3]); }),
-               med([](auto* x) { return (double)(x[4] - x[0]); }),
-               med([](auto* x) { return (double)x[7] / 100.0; }));
-  return MSFNO_OK;
 }
 
 bool mlp_fused_env() {
@@ -769,28 +680,14 @@ int launch_mlp_fused(const float* x1, const float* scale, const float* shift, co
     const char* e = getenv("MSFNO_MF_SCHED");
     return e ? atoi(e) : 1;
   }();
-  static const bool stamps = [] {
-    const char* e = getenv("MSFNO_MF_STAMPS");
-    return e && e[0] == '1';
-  }();
   // MSFNO_MF_AHEAD=1|3: A-fragment read-ahead depth (default 2), for A/B
   static const int ahead = [] {
     const char* e = getenv("MSFNO_MF_AHEAD");
     return e ? atoi(e) : 2;
   }();
-  // MSFNO_MF_XS=1: cross-step A-fragment prefetch (the next slice's barrier inside the
-  // current step), for A/B
-  static const int xs = [] {
-    const char* e = getenv("MSFNO_MF_XS");
-    return e ? atoi(e) : 0;
-  }();
-  if (stamps) return mlp_fused_stamped(p, tiles, sched, s);
   const dim3 grid((unsigned)tiles), blk(256);
-  if (xs)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 2, 1>), grid, blk, 0, s, p);
-  else if (!sched)
+  if (!sched)
     hipLaunchKernelGGL((mlp_fused_kernel<0, 0, 0, 2>), grid, blk, 0, s, p);
-
   else if (ahead == 1)
     hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 1>), grid, blk, 0, s, p);
   else if (ahead == 3)

@@ -1153,15 +1153,7 @@ int launch_skip_h(const float* W, const float* xs, const float* x, float* out, c
     hipLaunchKernelGGL(skip_hp_kernel, dim3((unsigned)grid), dim3(64 * SP_W), 0, s, q);
     return launch_check("skip_hp");
   }
-  // MSFNO_SKIP_NS=3: three ring slots, three workgroups per CU (A/B)
-  static const int ns = [] {
-    const char* e = getenv("MSFNO_SKIP_NS");
-    return e && e[0] == '3' ? 3 : 4;
-  }();
-  if (ns == 3)
-    hipLaunchKernelGGL((skip_h_kernel<3, 3>), dim3((unsigned)tiles), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((skip_h_kernel<MH_NS, 2>), dim3((unsigned)tiles), dim3(256), 0, s, p);
+  hipLaunchKernelGGL((skip_h_kernel<MH_NS, 2>), dim3((unsigned)tiles), dim3(256), 0, s, p);
   return launch_check("skip_h");
 }
 

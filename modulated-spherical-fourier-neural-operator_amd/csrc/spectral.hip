@@ -68,32 +68,6 @@ __global__ __launch_bounds__(256) void transpose_fwd_kernel(const float2* __rest
   }
 }
 
-__global__ void dc_fixup_kernel(float* __restrict__ Xt, int B, int C, int nlat, int ldk,
-                                const float* __restrict__ nscale,
-                                const float* __restrict__ nshift) {
-  const int64_t R = 2LL * B * C;
-  const int64_t n = R * nlat;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n;
-       e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = e / nlat;
-    const int k = (int)(e - r * nlat);
-    const int b = (int)(r / (2 * C));
-    const int ri = (int)((r / C) & 1);
-    const int c = (int)(r % C);
-    const int bc = b * C + c;
-    float* p = Xt + r * ldk + k;
-    *p = ri ? nscale[bc] * *p : fmaf(nscale[bc], *p, kTwoPi * nshift[bc]);
-  }
-}
-
-int launch_dc_fixup(float* Xt, int B, int C, int nlat, int ldk, const float* nscale,
-                    const float* nshift, hipStream_t s) {
-  const int64_t n = 2LL * B * C * nlat;
-  hipLaunchKernelGGL(dc_fixup_kernel, dim3((unsigned)std::min<int64_t>(cdiv(n, 256), 4096)),
-                     dim3(256), 0, s, Xt, B, C, nlat, ldk, nscale, nshift);
-  return launch_check("dc_fixup");
-}
-
 int launch_transpose_fwd(const float2* Xn, float* Xt, int B, int C, int nlat, int mmax, int ldk,
                          const float* nscale, const float* nshift, hipStream_t s,
                          const int* slab, int kpad) {
@@ -1622,7 +1596,7 @@ static int launch_contract_t(const float* a, const float* w, float* y, int B, in
 }
 
 // Batch 1 (the weight is read exactly once): the weight stream goes HBM -> LDS by
-// LDS-DMA (dma.h), NS - 1 channel steps ahead (MSFNO_CONTRACT_NS, default 2; 2 % faster
+// LDS-DMA (dma.h), NS - 1 channel steps ahead (NS = 2; 2 % faster
 // than the register-load kernel below, which batches > 1 use).  A workgroup owns 256 modes (one per
 // thread) and 16 output channels; a stage holds, for one input channel i, the 16
 // weight rows w[k0 + s, i, n0 .. n0 + 255] and the activation row a[i, n0 ..] (17
@@ -1713,19 +1687,9 @@ int launch_compl_contract(const float* a, const float* w, float* y, int B, int C
     const int nkc = (int)cdiv(Co, CDMA_KC);
     const int64_t nmt = cdiv(T, CDMA_NT);
     MSFNO_REQUIRE(nmt * nkc < (1LL << 31), MSFNO_EINVAL, "contract grid too large");
-    static const int ns = [] {
-      const char* e = getenv("MSFNO_CONTRACT_NS");
-      return e ? atoi(e) : 2;  // two 68-KB workgroups per CU: 5.88 ms vs 6.16 (3) / 6.19 (4)
-    }();
-    if (ns == 2)
-      hipLaunchKernelGGL(compl_contract_dma_kernel<2>, dim3((unsigned)(nmt * nkc)), dim3(256), 0,
-                         s, a, w, y, Ci, Co, T, nkc);
-    else if (ns == 4)
-      hipLaunchKernelGGL(compl_contract_dma_kernel<4>, dim3((unsigned)(nmt * nkc)), dim3(256), 0,
-                         s, a, w, y, Ci, Co, T, nkc);
-    else
-      hipLaunchKernelGGL(compl_contract_dma_kernel<3>, dim3((unsigned)(nmt * nkc)), dim3(256), 0,
-                         s, a, w, y, Ci, Co, T, nkc);
+    // two stages = two 68-KB workgroups per CU: 5.88 ms vs 6.16 (3 stages) / 6.19 (4)
+    hipLaunchKernelGGL(compl_contract_dma_kernel<2>, dim3((unsigned)(nmt * nkc)), dim3(256), 0,
+                       s, a, w, y, Ci, Co, T, nkc);
     return launch_check("compl_contract_dma");
   }
   const bool even = (T % 2 == 0) && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) |

@@ -5,7 +5,7 @@ golden blocks (tests/golden/make_golden.py) in a child process with its
 environment and reports the max-abs error; the bar is the same as the default
 path's (max-abs < 1e-4).  The cases cover the non-linear filter with FiLM on a
 180-longitude grid, a batch of two fields, and the linear filter on a 121x240
-Legendre-Gauss grid (whose 29,040 pixels end in a ragged 112-pixel MLP chunk)."""
+Legendre-Gauss grid."""
 import json
 import os
 import subprocess
@@ -25,7 +25,6 @@ VARIANTS = [
     {"MSFNO_X6P_WAVES": "4"},
     {"MSFNO_X6P_WAVES": "4x128"},
     {"MSFNO_X6P_MFMA": "16"},
-    {"MSFNO_MLP_CHUNK": "256"},
     {"MSFNO_R2C_CFG": "8x3", "MSFNO_C2R_WV": "4", "MSFNO_C2R_AREG": "0"},
     {"MSFNO_C2R_AREG": "0"},
     {"MSFNO_R2C_CFG": "16x1"},
@@ -33,13 +32,7 @@ VARIANTS = [
     {"MSFNO_SIDE_STREAM": "0"},
     {"MSFNO_GEMM": "f32"},
     {"MSFNO_CONTRACT_DMA": "0"},
-    {"MSFNO_CONTRACT_NS": "3"},
     {"MSFNO_CX16": "0"},
-    {"MSFNO_SPEC_L0F32": "0"},
-    {"MSFNO_X6C_TILED": "0"},
-    {"MSFNO_MF_XS": "1"},
-    {"MSFNO_X6C_WAVES": "24", "MSFNO_X6C_TILED": "0"},
-    {"MSFNO_X6C_WAVES": "4", "MSFNO_X6C_TILED": "0"},
     {"MSFNO_TR_FWD": "2p", "MSFNO_TR_INV": "2p"},
     {"MSFNO_TR_INV": "16x128"},
     {"MSFNO_SIDE_CUSTRIDE": "3"},
@@ -58,14 +51,13 @@ VARIANTS = [
     {"MSFNO_TR_FWD_PRE": "0", "MSFNO_TR_INV_BF": "0"},
     # older switches no test exercised before
     {"MSFNO_FFT_DMA": "0"},
-    {"MSFNO_FFT_TILE": "1", "MSFNO_NO_SYM": "1"},
+    {"MSFNO_NO_SYM": "1"},
     {"MSFNO_SIDE_PRIO": "normal"},
-    {"MSFNO_SPEC_4M": "1"},
-    {"MSFNO_SPEC_X6": "0", "MSFNO_C3M_TILE": "0"},
+    {"MSFNO_SPEC_X6": "0"},
     {"MSFNO_WCACHE": "0"},
     {"MSFNO_ENGINE": "x6", "MSFNO_MF_SCHED": "0"},
     {"MSFNO_ENGINE": "x6", "MSFNO_MF_AHEAD": "3"},
-    {"MSFNO_ENGINE": "x6", "MSFNO_X6_TILE": "4"},
+    {"MSFNO_ENGINE": "x6"},
     {"MSFNO_C2R_SWZ": "1"},
 ]
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of runtime switches in the full block: each argument is a list of VAR=value
-# assignments separated by ';' (e.g. "MSFNO_SPEC_4M=1;MSFNO_TILES=fc2=0"), one bench per argument.
+# assignments separated by ';' (e.g. "MSFNO_SPEC_3M=0;MSFNO_CX16=0"), one bench per argument.
 mkdir -p gpurun_out/sweep
 for cfg in "$@"; do
   ( IFS=';'; for kv in $cfg; do export "$kv"; done
