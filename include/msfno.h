@@ -330,6 +330,29 @@ int msfno_mlp_backward_input(const msfno_mlp_desc* d, const float* x, const floa
                              size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Sphere-weighted training losses (MSFNO/Models/losses.py:6-28, 80-155: CosineMSELoss,
+ * L2Sphere, L2Sphere_noSine, built at MSFNO/Models/train.py:434-446 and called once per
+ * training step at :162, :229, :283; the validation MSEs of :553-564).  All of them are
+ * per (b, c)
+ *   num = sum_h w_lat[h] sum_x (prd - tar)^2,    den = sum_h w_lat[h] sum_x tar^2
+ * under different latitude weights, finished by a few ops on the (B, C) sums (the Python
+ * mirror msfno_amd/losses.py).  prd, tar (BC, nlat, nlon) fp32, w_lat (nlat) fp32.  A
+ * latitude band passes its own rows and their weights; the sums of the bands add up.
+ * The reduction is deterministic (no atomics: fp32 partials per chunk of rows, combined
+ * per (b, c) in fp64 in a fixed order).  The workspace may hold anything on entry.
+ *   msfno_loss_sums:     sums (BC, 2) = {num, den}
+ *   msfno_loss_backward: dprd = 2 gnum[bc] w_lat[h] (prd - tar), gnum (BC) = dL/d num
+ *     (the target takes no gradient, as in the reference)
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+size_t msfno_loss_workspace_size(int BC, int nlat, int nlon);
+int msfno_loss_sums(const float* prd, const float* tar, const float* w_lat, float* sums, int BC,
+                    int nlat, int nlon, void* ws, size_t ws_bytes, void* stream);
+int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
+                        const float* gnum, float* dprd, int BC, int nlat, int nlon,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------
  * Latitude-band sharded SFNO-Block (multi-GPU form of
  * msfno_block_forward).  The reference runs one block per process on the whole
  * field (DDP = replicas, MSFNO/main.py:1153); this splits ONE field batch over

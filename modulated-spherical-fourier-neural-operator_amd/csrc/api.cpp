@@ -1533,6 +1533,29 @@ int msfno_conv1x1(const float* w, const float* bias, const float* x, float* out,
                  (int64_t)Cout * P, B, e, rest, ws_bytes - xs_bytes, s);
 }
 
+size_t msfno_loss_workspace_size(int BC, int nlat, int nlon) {
+  if (BC <= 0 || nlat <= 0 || nlon <= 0) return 0;
+  return loss_workspace_bytes(BC, nlat, nlon);
+}
+
+int msfno_loss_sums(const float* prd, const float* tar, const float* w_lat, float* sums, int BC,
+                    int nlat, int nlon, void* ws, size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(prd && tar && w_lat && sums && ws && BC > 0 && nlat > 0 && nlon > 0,
+                MSFNO_EINVAL, "bad loss_sums arguments");
+  MSFNO_REQUIRE(ws_bytes >= msfno_loss_workspace_size(BC, nlat, nlon), MSFNO_EWORKSPACE,
+                "loss_sums: workspace too small");
+  return launch_loss_sums(prd, tar, w_lat, sums, BC, nlat, nlon, ws, (hipStream_t)stream);
+}
+
+int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
+                        const float* gnum, float* dprd, int BC, int nlat, int nlon,
+                        void* stream) {
+  MSFNO_REQUIRE(prd && tar && w_lat && gnum && dprd && BC > 0 && nlat > 0 && nlon > 0,
+                MSFNO_EINVAL, "bad loss_backward arguments");
+  return launch_loss_backward(prd, tar, w_lat, gnum, dprd, BC, nlat, nlon,
+                              (hipStream_t)stream);
+}
+
 size_t msfno_block_wcache_size(const msfno_block_desc* d) {
   if (!d) return 0;
   msfno_block_desc t = *d;

@@ -146,6 +146,16 @@ int launch_gelu_grad_mul(float* dh, const float* pre, int64_t n, hipStream_t s);
 int launch_film_grad_reduce(const float* du, const float* x1, const float* an, const float* tn,
                             float scale, int BC, int64_t P, float* dgamma, float* dbeta,
                             hipStream_t s);
+// ---- loss.hip: sphere-weighted loss sums and their gradient -----------------------------
+// sums[bc] = {sum_h w[h] sum_x (prd - tar)^2, sum_h w[h] sum_x tar^2}; prd, tar (BC, nlat,
+// nlon); ws >= loss_workspace_bytes (may hold anything on entry)
+size_t loss_workspace_bytes(int BC, int nlat, int nlon);
+int launch_loss_sums(const float* prd, const float* tar, const float* w_lat, float* sums, int BC,
+                     int nlat, int nlon, void* ws, hipStream_t s);
+// dprd[bc][h][x] = 2 gnum[bc] w[h] (prd - tar)
+int launch_loss_backward(const float* prd, const float* tar, const float* w_lat,
+                         const float* gnum, float* dprd, int BC, int nlat, int nlon,
+                         hipStream_t s);
 // full block backward (block_bwd.cpp): per-row InstanceNorm moments and affine,
 // InstanceNorm backward (with the FiLM factor 1 + gamma s and up to two addends),
 // ComplexReLU(real) mask, complex conjugate transposes, tril <-> dense spectra, fill

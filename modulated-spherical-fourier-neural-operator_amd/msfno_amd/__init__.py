@@ -9,5 +9,6 @@ from . import _native  # noqa: F401
 from . import harmonics  # noqa: F401
 from . import sfno  # noqa: F401
 from . import rollout  # noqa: F401
+from . import losses  # noqa: F401
 
 __version__ = "0.1.0"
