@@ -353,6 +353,25 @@ int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
                         void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Per-degree power spectrum of spherical-harmonic coefficients and its gradient: the
+ * middle step of the reference's spectral losses (MSFNO/Models/losses.py:158-232,
+ * spectral_l2loss_sphere, spectral_loss_sphere, h1loss_sphere; the Python mirror is
+ * msfno_amd/losses.py) and a per-degree diagnostic of a rollout.  The weight 2 applies to
+ * every m >= 1 (Nyquist included) and all m of a row are read: coeffs is any complex
+ * tensor, not only a transform's output.  No workspace, no atomics: the result is bitwise
+ * reproducible.  MSFNO_EINVAL for null pointers, an extent below 1, or coefficient
+ * pointers off the 8-byte grid of a complex tensor.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+/* power[n][l] = |c[n][l][0]|^2 + 2 * sum_{m>=1} |c[n][l][m]|^2
+ * coeffs (N, lmax, mmax) complex64 interleaved, power (N, lmax) fp32 */
+int msfno_spectrum_power(const float* coeffs, float* power, long long N, int lmax, int mmax,
+                         void* stream);
+/* dcoeffs[n][l][m] = (2 e_m gpower[n][l]) * coeffs[n][l][m], e_0 = 1, e_m = 2 (m >= 1) */
+int msfno_spectrum_power_backward(const float* coeffs, const float* gpower, float* dcoeffs,
+                                  long long N, int lmax, int mmax, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Latitude-band sharded SFNO-Block (multi-GPU form of
  * msfno_block_forward).  The reference runs one block per process on the whole
  * field (DDP = replicas, MSFNO/main.py:1153); this splits ONE field batch over

@@ -1556,6 +1556,29 @@ int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
                               (hipStream_t)stream);
 }
 
+// N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on
+// the 8-byte grid
+static bool spectrum_args_ok(const void* a, const void* b, long long N, int lmax, int mmax) {
+  return a && b && N >= 1 && lmax >= 1 && mmax >= 1 &&
+         ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7) == 0 &&
+         N <= INT64_MAX / ((int64_t)lmax * mmax * 2);
+}
+
+int msfno_spectrum_power(const float* coeffs, float* power, long long N, int lmax, int mmax,
+                         void* stream) {
+  MSFNO_REQUIRE(power && spectrum_args_ok(coeffs, coeffs, N, lmax, mmax), MSFNO_EINVAL,
+                "bad spectrum_power arguments");
+  return launch_spectrum_power(coeffs, power, (int64_t)N * lmax, mmax, (hipStream_t)stream);
+}
+
+int msfno_spectrum_power_backward(const float* coeffs, const float* gpower, float* dcoeffs,
+                                  long long N, int lmax, int mmax, void* stream) {
+  MSFNO_REQUIRE(gpower && spectrum_args_ok(coeffs, dcoeffs, N, lmax, mmax), MSFNO_EINVAL,
+                "bad spectrum_power_backward arguments");
+  return launch_spectrum_power_backward(coeffs, gpower, dcoeffs, (int64_t)N * lmax, mmax,
+                                        (hipStream_t)stream);
+}
+
 size_t msfno_block_wcache_size(const msfno_block_desc* d) {
   if (!d) return 0;
   msfno_block_desc t = *d;

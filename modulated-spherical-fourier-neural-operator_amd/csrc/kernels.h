@@ -156,6 +156,14 @@ int launch_loss_sums(const float* prd, const float* tar, const float* w_lat, flo
 int launch_loss_backward(const float* prd, const float* tar, const float* w_lat,
                          const float* gnum, float* dprd, int BC, int nlat, int nlon,
                          hipStream_t s);
+// ---- spectrum.hip: per-degree power spectrum and its gradient ----------------------------
+// coeffs (rows, mmax) complex interleaved, 8-byte aligned, rows = N * lmax:
+// power[r] = |c[r][0]|^2 + 2 sum_{m >= 1} |c[r][m]|^2
+int launch_spectrum_power(const float* coeffs, float* power, int64_t rows, int mmax,
+                          hipStream_t s);
+// dcoeffs[r][m] = (2 e_m gpower[r]) coeffs[r][m], e_0 = 1, e_m = 2 (m >= 1)
+int launch_spectrum_power_backward(const float* coeffs, const float* gpower, float* dcoeffs,
+                                   int64_t rows, int mmax, hipStream_t s);
 // full block backward (block_bwd.cpp): per-row InstanceNorm moments and affine,
 // InstanceNorm backward (with the FiLM factor 1 + gamma s and up to two addends),
 // ComplexReLU(real) mask, complex conjugate transposes, tril <-> dense spectra, fill

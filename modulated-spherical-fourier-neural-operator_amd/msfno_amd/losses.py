@@ -13,6 +13,11 @@ reference's semantics.  The target takes no gradient, as in the reference's trai
 
 ``weighted_sums(prd, tar, w)`` is the band-local entry: a latitude-band rank passes its
 own rows and ``w[rows]`` and all-reduces the (B, C, 2) result.
+
+The spectral losses of ``losses.py:158-232`` (``spectral_l2loss_sphere``,
+``spectral_loss_sphere``, ``h1loss_sphere``) are at the end of this module: a
+differentiable forward transform, the native per-degree power spectrum and torch ops on
+the spectra; there the target may require grad.
 """
 from __future__ import annotations
 
@@ -21,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from . import harmonics as _harmonics
 from .harmonics import quadrature
 
 KINDS = ("l2sphere", "l2sphere_nosine", "cosine", "uniform")
@@ -195,3 +201,69 @@ def per_variable_mse(prd, tar):
     B, C, H, W = prd.shape
     s = weighted_sums(prd, tar, device_weights("uniform", H, prd.device))
     return s[..., 0].sum(dim=0) / (B * H * W)
+
+
+# ---- spectral losses (MSFNO/Models/losses.py:158-232) ---------------------------------
+# Each is the forward transform of prd - tar (subtracted on the grid first, as the
+# reference does: that keeps the conditioning when prd is close to tar), the per-degree
+# power spectrum of the coefficients (harmonics.power_spectrum, csrc/spectrum.hip) and
+# plain torch on the (..., C, lmax) spectra.  Both native steps are autograd ops, so the
+# reference's semantics follow, a target that requires grad included.  As in the
+# reference the sum runs over the last two dimensions of the spectra -- degree AND channel
+# (losses.py:163: norm2 is (B, C, lmax)) -- before ``relative`` / ``squared``, and the
+# result is the mean over what remains (the batch).
+
+def _forward_transform(solver):
+    """The transform of a reference-style solver (``solver.sht``) or the transform
+    itself; one of another library (torch-harmonics) is adopted, its table shared."""
+    return _harmonics.adopt(getattr(solver, "sht", solver), inverse=False)
+
+
+def _degree_spectrum(sht, field):
+    if not field.is_cuda:
+        raise ValueError("prd and tar must be GPU (HIP) tensors; libmsfno has no CPU path")
+    return _harmonics.power_spectrum(sht(field))
+
+
+def _degree_weights(sht, device):
+    ls = torch.arange(sht.lmax).float()  # l (l + 1) in fp32, as the reference forms it
+    return (ls * (ls + 1)).to(device)
+
+
+def _finish(loss, squared):
+    if not squared:
+        loss = torch.sqrt(loss)
+    return loss.mean()
+
+
+def spectral_l2loss_sphere(solver, prd, tar, relative=False, squared=True):
+    """losses.py:158-176: the L2 norm of prd - tar from its spectrum."""
+    sht = _forward_transform(solver)
+    loss = _degree_spectrum(sht, prd - tar).sum(dim=(-1, -2))
+    if relative:
+        loss = loss / _degree_spectrum(sht, tar).sum(dim=(-1, -2))
+    return _finish(loss, squared)
+
+
+def spectral_loss_sphere(solver, prd, tar, relative=False, squared=True):
+    """losses.py:178-203: the same under the weights l (l + 1) (the H1 seminorm)."""
+    sht = _forward_transform(solver)
+    w = _degree_weights(sht, prd.device)
+    loss = (w * _degree_spectrum(sht, prd - tar)).sum(dim=(-1, -2))
+    if relative:
+        loss = loss / (w * _degree_spectrum(sht, tar)).sum(dim=(-1, -2))
+    return _finish(loss, squared)
+
+
+def h1loss_sphere(solver, prd, tar, relative=False, squared=True):
+    """losses.py:205-232: seminorm + L2 norm (of the roots unless ``squared``: "strictly
+    speaking this is not exactly h1 loss", :220)."""
+    if relative:
+        raise NotImplementedError("Relative H1 loss not implemented")
+    sht = _forward_transform(solver)
+    power = _degree_spectrum(sht, prd - tar)
+    h1 = (_degree_weights(sht, prd.device) * power).sum(dim=(-1, -2))
+    l2 = power.sum(dim=(-1, -2))
+    if not squared:
+        return (torch.sqrt(h1) + torch.sqrt(l2)).mean()
+    return (h1 + l2).mean()

@@ -262,7 +262,7 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
         Nyquist bins) and an inverse plan on the input grid with table weights d_m 2pi /
         nlon_in (the adjoint of 2pi rfft(norm="forward"): d_m = 1/2 but DC and Nyquist).
         Rebuilt only when a transform table tensor changes."""
-        import math
+        from ..harmonics.sht import adjoint_table
         fwd, inv = self._transforms()
         idx = device.index if device.index is not None else torch.cuda.current_device()
         key = (idx,) + tuple((t.data_ptr(), t._version, t.dtype, str(t.device))
@@ -270,17 +270,8 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
         cache = getattr(self, "_adj", None)
         if cache is not None and cache[0] == key:
             return cache[1], cache[2]
-        mmax = fwd.mmax
-        m = torch.arange(mmax, dtype=torch.float64)
-
-        def weights(n, inner, edge):
-            w = torch.full((mmax,), inner, dtype=torch.float64)
-            w[(m == 0) | (2 * m == n)] = edge
-            return w[:, None, None]
-        t1 = (inv.pct.detach().double().cpu() * weights(inv.nlon, 2.0, 1.0)
-              * (inv.nlon / (2 * math.pi))).float().to(device).contiguous()
-        t2 = (fwd.weights.detach().double().cpu() * weights(fwd.nlon, 0.5, 1.0)
-              * (2 * math.pi / fwd.nlon)).float().to(device).contiguous()
+        t1 = adjoint_table(inv.pct, inv.nlon, True).to(device).contiguous()
+        t2 = adjoint_table(fwd.weights, fwd.nlon, False).to(device).contiguous()
         fa = N.SHTPlan(inv.nlat, inv.nlon, inv.lmax, inv.mmax, False, idx)
         fa.load(t1, key)
         ga = N.SHTPlan(fwd.nlat, fwd.nlon, fwd.lmax, fwd.mmax, True, idx)
