@@ -353,6 +353,31 @@ int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
                         void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Forecast verification: the sums behind RMSE, bias, MAE, the climatology skill score and
+ * the anomaly correlation of a rollout (MSFNO/Models/sfno/model.py:737-758 and
+ * train.py:533-583 form them on the host after copying every scored output there; the
+ * Python mirror is msfno_amd/verification.py).  One pass over prd, tar (BC, nlat, nlon)
+ * fp32 and an optional climatology, all in one (real) space; per (b, c) under w_lat (nlat)
+ *   sums[bc] = { se    = sum w (p - t)^2,   err   = sum w (p - t),   ae = sum w |p - t|,
+ *                pa2   = sum w (p - c)^2,   ta2   = sum w (t - c)^2,
+ *                cross = sum w (p - c)(t - c) }
+ * clim is a stack of (nlat, nlon) fp32 slabs and clim_slab a device int32[BC]: the slab
+ * index of bc (not range-checked), or -1 for none; both NULL for no climatology at all.
+ * A slab without one gets pa2 = ta2 = cross = 0 exactly, and every word of sums is
+ * written by every call.  A latitude band passes its own rows, their weights and the same
+ * rows of clim; the sums of the bands add up.  Deterministic as msfno_loss_sums (no
+ * atomics, fp32 partials combined per (b, c) in fp64 in a fixed order); the workspace may
+ * hold anything on entry; nothing allocates, synchronises or memsets, so the call records
+ * into a graph.  MSFNO_EINVAL for null required pointers, an extent below 1, or only one
+ * of clim / clim_slab; MSFNO_EWORKSPACE for a short workspace; both before any launch.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+size_t msfno_verify_workspace_size(int BC, int nlat, int nlon);
+int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, const float* clim,
+                      const int* clim_slab, float* sums /* (BC, 6) */, int BC, int nlat,
+                      int nlon, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-degree power spectrum of spherical-harmonic coefficients and its gradient: the
  * middle step of the reference's spectral losses (MSFNO/Models/losses.py:158-232,
  * spectral_l2loss_sphere, spectral_loss_sphere, h1loss_sphere; the Python mirror is

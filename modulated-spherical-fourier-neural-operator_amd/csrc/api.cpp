@@ -1556,6 +1556,24 @@ int msfno_loss_backward(const float* prd, const float* tar, const float* w_lat,
                               (hipStream_t)stream);
 }
 
+size_t msfno_verify_workspace_size(int BC, int nlat, int nlon) {
+  if (BC <= 0 || nlat <= 0 || nlon <= 0) return 0;
+  return verify_workspace_bytes(BC, nlat, nlon);
+}
+
+int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, const float* clim,
+                      const int* clim_slab, float* sums, int BC, int nlat, int nlon, void* ws,
+                      size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(prd && tar && w_lat && sums && ws && BC > 0 && nlat > 0 && nlon > 0,
+                MSFNO_EINVAL, "bad verify_sums arguments");
+  MSFNO_REQUIRE((clim == nullptr) == (clim_slab == nullptr), MSFNO_EINVAL,
+                "verify_sums: clim and clim_slab must both be set or both be null");
+  MSFNO_REQUIRE(ws_bytes >= msfno_verify_workspace_size(BC, nlat, nlon), MSFNO_EWORKSPACE,
+                "verify_sums: workspace too small");
+  return launch_verify_sums(prd, tar, w_lat, clim, clim_slab, sums, BC, nlat, nlon, ws,
+                            (hipStream_t)stream);
+}
+
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on
 // the 8-byte grid
 static bool spectrum_args_ok(const void* a, const void* b, long long N, int lmax, int mmax) {

@@ -156,6 +156,14 @@ int launch_loss_sums(const float* prd, const float* tar, const float* w_lat, flo
 int launch_loss_backward(const float* prd, const float* tar, const float* w_lat,
                          const float* gnum, float* dprd, int BC, int nlat, int nlon,
                          hipStream_t s);
+// ---- verify.hip: forecast verification sums -----------------------------------------------
+// sums[bc] = {se, err, ae, pa2, ta2, cross} (see verify.hip); clim a stack of (nlat, nlon)
+// slabs and clim_slab (BC) device int32 slab indices, -1 = none, or both null;
+// ws >= verify_workspace_bytes (may hold anything on entry)
+size_t verify_workspace_bytes(int BC, int nlat, int nlon);
+int launch_verify_sums(const float* prd, const float* tar, const float* w_lat, const float* clim,
+                       const int* clim_slab, float* sums, int BC, int nlat, int nlon, void* ws,
+                       hipStream_t s);
 // ---- spectrum.hip: per-degree power spectrum and its gradient ----------------------------
 // coeffs (rows, mmax) complex interleaved, 8-byte aligned, rows = N * lmax:
 // power[r] = |c[r][0]|^2 + 2 sum_{m >= 1} |c[r][m]|^2

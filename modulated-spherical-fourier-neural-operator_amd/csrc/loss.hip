@@ -8,68 +8,27 @@
 // backward at 1 x 73 x 721 x 1440), so: 16-byte loads / stores on the part of a row where
 // every pointer involved is 16-byte aligned (scalar head and tail; a slab with odd
 // nlat * nlon moves the alignment from row to row), work units of (bc, chunk of rows)
-// on a capped grid, and no atomics: per-lane fp32 sums of a row's squares, weighted once
+// on a capped grid (row_geom.h, shared with verify.hip), and no atomics: per-lane fp32 sums of a row's squares, weighted once
 // per row, wave + block reduce, one partial per unit into the caller's workspace, combined
 // per (b, c) in fp64 in a fixed order by a second kernel.  Every workspace word read is
 // written by the same call.
 #include "kernels.h"
+#include "row_geom.h"
 
 namespace msfno {
 
-namespace {
-constexpr int kLossThreads = 256;
-constexpr int kLossMaxRows = 64;    // rows per unit: bounds a lane's fp32 chain (below)
-constexpr int kLossGridCap = 2048;  // 8 workgroups per CU
-
-// A workgroup is 256 / lpr row groups of lpr lanes (whole waves); a group sweeps one row
-// at a time, 4 floats per lane.  lpr: the one of 256, 128, 64 with the fewest idle lane
-// slots over the row (1440: 360 float4 = 3 sweeps of 128, not 2 of 256 with the second
-// 40 % full).
-struct LossGeom {
-  int lpr;      // lanes per row group
-  int rows;     // rows per unit (a multiple of the group count unless one unit has them all)
-  int chunks;   // units per (b, c) slab
-};
-
-LossGeom loss_geom(int BC, int nlat, int nlon) {
-  LossGeom g;
-  const int nvec = std::max(1, nlon / 4);
-  g.lpr = 256;
-  for (int l = 128; l >= 64; l >>= 1)
-    if (cdiv(nvec, l) * l < cdiv(nvec, g.lpr) * g.lpr) g.lpr = l;
-  const int ngrp = kLossThreads / g.lpr;
-  // enough units to fill the chip at small BC, at most kLossMaxRows rows each: a lane's
-  // sequential fp32 chain is its share of a row (nlon / lpr terms) plus one weighted add
-  // per row it visits, <= 128 terms for nlon <= 16384
-  int64_t chunks = std::max<int64_t>(cdiv(kLossGridCap, BC), cdiv(nlat, kLossMaxRows));
-  chunks = std::min<int64_t>(chunks, nlat);
-  g.rows = (int)std::min<int64_t>(round_up(cdiv(nlat, chunks), ngrp), kLossMaxRows);
-  g.chunks = (int)cdiv(nlat, g.rows);
-  return g;
-}
-
-__device__ __forceinline__ int misalign4(const float* p) {
-  return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);
-}
-}  // namespace
-
-// Upper bound of BC * chunks that is non-decreasing in every argument (BC * chunks itself
-// is not: more slabs means fewer chunks each): chunks <= nlat and
-// chunks <= cdiv(cap, BC) + cdiv(nlat, maxrows).
 size_t loss_workspace_bytes(int BC, int nlat, int nlon) {
   (void)nlon;
-  const int64_t a = (int64_t)BC * nlat;
-  const int64_t b = kLossGridCap + (int64_t)BC + (int64_t)BC * cdiv(nlat, kLossMaxRows);
-  return (size_t)round_up(std::min(a, b) * (int64_t)sizeof(float2), 256);
+  return (size_t)round_up(row_units_bound(BC, nlat) * (int64_t)sizeof(float2), 256);
 }
 
-__global__ __launch_bounds__(kLossThreads) void loss_sums_kernel(
+__global__ __launch_bounds__(kRowThreads) void loss_sums_kernel(
     const float* __restrict__ prd, const float* __restrict__ tar,
     const float* __restrict__ w_lat, float2* __restrict__ part, int nlat, int nlon, int chunks,
     int rows, int64_t units, int lpr) {
-  __shared__ float2 red[kLossThreads / 64];
+  __shared__ float2 red[kRowThreads / 64];
   const int grp = (int)threadIdx.x / lpr, lane = (int)threadIdx.x % lpr;
-  const int ngrp = kLossThreads / lpr;
+  const int ngrp = kRowThreads / lpr;
   for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
     const int64_t bc = u / chunks;
     const int h0 = (int)(u - bc * chunks) * rows, h1 = min(nlat, h0 + rows);
@@ -124,7 +83,7 @@ __global__ __launch_bounds__(kLossThreads) void loss_sums_kernel(
     __syncthreads();
     if (threadIdx.x == 0) {
       float2 s = red[0];
-      for (int k = 1; k < kLossThreads / 64; ++k) {
+      for (int k = 1; k < kRowThreads / 64; ++k) {
         s.x += red[k].x;
         s.y += red[k].y;
       }
@@ -135,9 +94,9 @@ __global__ __launch_bounds__(kLossThreads) void loss_sums_kernel(
 }
 
 // one wave per (b, c): lane l adds the partials l, l + 64, ... in fp64, then a fixed tree
-__global__ __launch_bounds__(kLossThreads) void loss_combine_kernel(
+__global__ __launch_bounds__(kRowThreads) void loss_combine_kernel(
     const float2* __restrict__ part, int chunks, int BC, float* __restrict__ sums) {
-  const int bc = (int)blockIdx.x * (kLossThreads / 64) + ((int)threadIdx.x >> 6);
+  const int bc = (int)blockIdx.x * (kRowThreads / 64) + ((int)threadIdx.x >> 6);
   if (bc >= BC) return;
   const int lane = threadIdx.x & 63;
   double n = 0.0, d = 0.0;
@@ -158,12 +117,12 @@ __global__ __launch_bounds__(kLossThreads) void loss_combine_kernel(
 
 // dprd = (2 gnum[bc] w[h]) (prd - tar): one rounding each for the coefficient (the
 // doubling is exact), the difference and the product
-__global__ __launch_bounds__(kLossThreads) void loss_backward_kernel(
+__global__ __launch_bounds__(kRowThreads) void loss_backward_kernel(
     const float* __restrict__ prd, const float* __restrict__ tar,
     const float* __restrict__ w_lat, const float* __restrict__ gnum, float* __restrict__ dprd,
     int nlat, int nlon, int chunks, int rows, int64_t units, int lpr) {
   const int grp = (int)threadIdx.x / lpr, lane = (int)threadIdx.x % lpr;
-  const int ngrp = kLossThreads / lpr;
+  const int ngrp = kRowThreads / lpr;
   for (int64_t u = blockIdx.x; u < units; u += gridDim.x) {
     const int64_t bc = u / chunks;
     const int h0 = (int)(u - bc * chunks) * rows, h1 = min(nlat, h0 + rows);
@@ -200,25 +159,25 @@ __global__ __launch_bounds__(kLossThreads) void loss_backward_kernel(
 
 int launch_loss_sums(const float* prd, const float* tar, const float* w_lat, float* sums, int BC,
                      int nlat, int nlon, void* ws, hipStream_t s) {
-  const LossGeom g = loss_geom(BC, nlat, nlon);
+  const RowGeom g = row_geom(BC, nlat, nlon);
   const int64_t units = (int64_t)BC * g.chunks;
   float2* part = static_cast<float2*>(ws);
-  const int blocks = (int)std::min<int64_t>(units, kLossGridCap);
-  hipLaunchKernelGGL(loss_sums_kernel, dim3(blocks), dim3(kLossThreads), 0, s, prd, tar, w_lat,
+  const int blocks = (int)std::min<int64_t>(units, kRowGridCap);
+  hipLaunchKernelGGL(loss_sums_kernel, dim3(blocks), dim3(kRowThreads), 0, s, prd, tar, w_lat,
                      part, nlat, nlon, g.chunks, g.rows, units, g.lpr);
   MSFNO_TRY(launch_check("loss_sums"));
-  hipLaunchKernelGGL(loss_combine_kernel, dim3((unsigned)cdiv(BC, kLossThreads / 64)),
-                     dim3(kLossThreads), 0, s, part, g.chunks, BC, sums);
+  hipLaunchKernelGGL(loss_combine_kernel, dim3((unsigned)cdiv(BC, kRowThreads / 64)),
+                     dim3(kRowThreads), 0, s, part, g.chunks, BC, sums);
   return launch_check("loss_combine");
 }
 
 int launch_loss_backward(const float* prd, const float* tar, const float* w_lat,
                          const float* gnum, float* dprd, int BC, int nlat, int nlon,
                          hipStream_t s) {
-  const LossGeom g = loss_geom(BC, nlat, nlon);
+  const RowGeom g = row_geom(BC, nlat, nlon);
   const int64_t units = (int64_t)BC * g.chunks;
-  const int blocks = (int)std::min<int64_t>(units, kLossGridCap);
-  hipLaunchKernelGGL(loss_backward_kernel, dim3(blocks), dim3(kLossThreads), 0, s, prd, tar,
+  const int blocks = (int)std::min<int64_t>(units, kRowGridCap);
+  hipLaunchKernelGGL(loss_backward_kernel, dim3(blocks), dim3(kRowThreads), 0, s, prd, tar,
                      w_lat, gnum, dprd, nlat, nlon, g.chunks, g.rows, units, g.lpr);
   return launch_check("loss_backward");
 }

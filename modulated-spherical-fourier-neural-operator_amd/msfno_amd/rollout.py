@@ -221,3 +221,43 @@ class Rollout:
             for i in range(steps):
                 x = self._step(x)
                 yield i, self.normalise(x, reverse=True)
+
+    def verify(self, x0, truths, steps, every=1, weights="uniform", normalised_input=False,
+               verifier=None):
+        """Score a rollout on the device (model.py:737-758, train.py:533-583 without the
+        per-step copy to the host): ``run(x0, steps)`` with every step ``i`` where
+        ``i % every == 0`` (``every = validation_step_skip + 1``, train.py:551) scored
+        against the next item of ``truths``: ``tar``, ``(tar, clim)`` or
+        ``(tar, clim, clim_slab)``, raw fields as ``verification.field_sums`` takes them
+        (host tensors are copied without blocking).  Returns ``verification.Scores`` of
+        (n_scored, B, C) tensors under ``weights`` (``verification.Verifier``).  Pass a
+        ``verifier`` of your own to keep the raw sums (``verifier.sums``) or to reuse its
+        buffers; its weights then apply."""
+        from . import verification as V
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.verify scores whole fields; on a latitude-band rank call "
+                "verification.field_sums on the rank's rows with w[rows] and "
+                "clim[..., rows, :], all-reduce the (B, C, 6) sums over the ranks, then "
+                "verification.finish with the whole grid's w")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        n_scored = (steps + every - 1) // every
+        if verifier is None:
+            B, C, H, W = x0.shape
+            verifier = V.Verifier(weights, H, W, n_scored, B, C, device=x0.device)
+        elif verifier.sums.shape[0] < n_scored:
+            raise ValueError(f"verifier has {verifier.sums.shape[0]} slots, {n_scored} needed")
+        truths = iter(truths)
+        for i, y in self.run(x0, steps, normalised_input=normalised_input):
+            if i % every:
+                continue
+            try:
+                item = next(truths)
+            except StopIteration:
+                raise ValueError(f"truths ran out at step {i}: {n_scored} scored steps need "
+                                 "one item each") from None
+            if isinstance(item, torch.Tensor):
+                item = (item,)
+            verifier.update(i // every, y, *item)
+        return verifier.scores()

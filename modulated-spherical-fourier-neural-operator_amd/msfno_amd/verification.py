@@ -1,0 +1,236 @@
+"""Forecast verification on the device: RMSE, bias, MAE, the climatology skill score and
+the anomaly correlation (ACC) of a rollout.
+
+The reference scores a forecast on the host: ``evaluate_model``
+(``MSFNO/Models/sfno/model.py:656-811``) and ``Trainer.validation`` (``train.py:533-583``)
+copy every scored output off the device (``model.py:741,748``), denormalise it and form
+per-variable MSEs and ``1 - MSE(prd, truth) / MSE(clim, truth)`` (``model.py:743-758``).
+Here one native pass (``msfno_verify_sums``, csrc/verify.hip) over the forecast, the truth
+and an optional climatology leaves six latitude-weighted sums per (batch, channel),
+
+    se = sum w (p-t)^2    err = sum w (p-t)       ae = sum w |p-t|
+    pa2 = sum w (p-c)^2   ta2 = sum w (t-c)^2     cross = sum w (p-c)(t-c)
+
+and ``finish`` turns them into scores with plain torch on (B, C) numbers.  The sums are
+additive over rows: a latitude-band rank calls ``field_sums`` on its own rows with
+``w[rows]`` and ``clim[..., rows, :]``, all-reduces the (B, C, 6) result and finishes with
+the whole grid's ``w``.
+
+``Verifier`` is the preallocated form for a rollout (one launch per scored step into a
+slot, nothing synchronises); ``Rollout.verify`` drives it.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import torch
+
+from . import _native as N
+from . import losses as _losses
+
+NSUMS = 6
+SE, ERR, AE, PA2, TA2, CROSS = range(NSUMS)
+
+Scores = namedtuple("Scores", ["mse", "rmse", "bias", "mae", "skill", "acc"])
+
+_slab_cache: dict = {}
+
+
+def _device_key(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _default_slabs(clim_dim, B, C, device):
+    """The slab map of a (C, H, W) climatology (broadcast over the batch) or a
+    (B, C, H, W) one; built on the device (no host copy), cached per (kind, B, C, device)."""
+    key = (clim_dim, B, C, _device_key(device))
+    m = _slab_cache.get(key)
+    if m is None:
+        if clim_dim == 3:
+            m = torch.arange(C, dtype=torch.int32, device=device).repeat(B)
+        else:
+            m = torch.arange(B * C, dtype=torch.int32, device=device)
+        _slab_cache[key] = m
+    return m
+
+
+def _weights(weights, nlat, device):
+    if isinstance(weights, str):
+        return _losses.device_weights(weights, nlat, device)
+    return weights
+
+
+def _check_fields(prd, tar, w):
+    if prd.dim() != 4 or prd.shape != tar.shape:
+        raise ValueError(f"prd and tar must be (B, C, H, W) of one shape, got "
+                         f"{tuple(prd.shape)} and {tuple(tar.shape)}")
+    for name, t in (("prd", prd), ("tar", tar), ("w", w)):
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad: the verification sums have no gradient; "
+                             f"pass {name}.detach() (for training use msfno_amd.losses)")
+    prd = N.require_device_f32(prd, "prd")
+    tar = N.require_device_f32(tar, "tar")
+    w = N.require_device_f32(w, "w")
+    if w.dim() != 1 or w.numel() != prd.shape[2]:
+        raise ValueError(f"w must hold one weight per latitude row ({prd.shape[2]}), got "
+                         f"{tuple(w.shape)}")
+    if not (prd.device == tar.device == w.device):
+        raise ValueError("prd, tar and w must be on one device")
+    if prd.numel() == 0:
+        raise ValueError("empty fields")
+    return prd, tar, w
+
+
+def _check_clim(clim, clim_slab, shape, device):
+    """(clim as (K, H, W), slab map as int32 (B C,)) on ``device``, or (None, None)."""
+    B, C, H, W = shape
+    if clim is None:
+        if clim_slab is not None:
+            raise ValueError("clim_slab without clim")
+        return None, None
+    if clim.requires_grad:
+        raise ValueError("clim requires grad: the verification sums have no gradient")
+    clim = N.require_device_f32(clim, "clim")
+    if clim.device != device:
+        raise ValueError("clim must be on the device of prd")
+    if clim_slab is None:
+        if tuple(clim.shape) not in ((C, H, W), (B, C, H, W)):
+            raise ValueError(f"clim must be (C, H, W) = {(C, H, W)} or (B, C, H, W) = "
+                             f"{(B, C, H, W)} without a clim_slab, got {tuple(clim.shape)}")
+        return clim.reshape(-1, H, W), _default_slabs(clim.dim(), B, C, device)
+    if clim.dim() != 3 or tuple(clim.shape[1:]) != (H, W) or clim.shape[0] < 1:
+        raise ValueError(f"clim must be (K, H, W) with (H, W) = {(H, W)} under a clim_slab, "
+                         f"got {tuple(clim.shape)}")
+    if not isinstance(clim_slab, torch.Tensor) or not clim_slab.is_cuda:
+        # a host map is range-checked here; a device map is trusted (checking it would
+        # synchronise)
+        host = torch.as_tensor(clim_slab, dtype=torch.int64).reshape(-1)
+        if host.numel() and (host.min() < -1 or host.max() >= clim.shape[0]):
+            raise ValueError(f"clim_slab entries must be -1 or in [0, {clim.shape[0]})")
+        clim_slab = host.to(torch.int32).to(device, non_blocking=True)
+    if clim_slab.dtype != torch.int32:
+        clim_slab = clim_slab.to(torch.int32)
+    clim_slab = clim_slab.reshape(-1).contiguous()
+    if clim_slab.numel() != B * C or clim_slab.device != device:
+        raise ValueError(f"clim_slab must hold B * C = {B * C} slab indices on the device of "
+                         f"prd, got {tuple(clim_slab.shape)} on {clim_slab.device}")
+    return clim, clim_slab
+
+
+def workspace(B: int, C: int, nlat: int, nlon: int, device) -> torch.Tensor:
+    """A workspace for ``msfno_verify_sums`` at this shape (contents do not matter)."""
+    return torch.empty(N.lib().msfno_verify_workspace_size(B * C, nlat, nlon),
+                       dtype=torch.uint8, device=device)
+
+
+@N.on_input_device
+def _launch(prd, tar, w, clim, clim_slab, out, ws):
+    B, C, H, W = prd.shape
+    N.check(N.lib().msfno_verify_sums(prd.data_ptr(), tar.data_ptr(), w.data_ptr(), N.ptr(clim),
+                                      N.ptr(clim_slab), out.data_ptr(), B * C, H, W,
+                                      ws.data_ptr(), ws.numel(), N.stream_of(prd.device)),
+            "msfno_verify_sums")
+    return out
+
+
+@torch.no_grad()
+def field_sums(prd, tar, w, clim=None, clim_slab=None) -> torch.Tensor:
+    """(B, C, 6) fp32 = {se, err, ae, pa2, ta2, cross} of (B, C, H, W) fp32 device fields
+    under the latitude weights ``w`` (any fp32 device vector of length H).
+
+    ``clim`` is (C, H, W) (one climatology for every sample) or (B, C, H, W); or, with an
+    explicit ``clim_slab`` (B * C slab indices, -1 for a slab without a climatology), a
+    (K, H, W) stack.  A device ``clim_slab`` is not range-checked.  Slabs without a
+    climatology get exact zeros in the last three sums.  No gradient."""
+    prd, tar, w = _check_fields(prd, tar, w)
+    clim, clim_slab = _check_clim(clim, clim_slab, prd.shape, prd.device)
+    B, C, H, W = prd.shape
+    out = torch.empty(B, C, NSUMS, dtype=torch.float32, device=prd.device)
+    return _launch(prd, tar, w, clim, clim_slab, out, workspace(B, C, H, W, prd.device))
+
+
+def finish(sums, w, nlon, batch_mean=False) -> Scores:
+    """Scores from (..., B, C, 6) sums (device or host, any float dtype) taken under the
+    weights ``w`` of the whole grid, with n = nlon * sum(w):
+
+        mse = se / n, rmse = sqrt(mse), bias = err / n, mae = ae / n,
+        skill = 1 - se / ta2  (model.py:757),  acc = cross / sqrt(pa2 ta2)
+
+    each of shape (..., B, C); ``skill`` and ``acc`` are NaN where the slab had no
+    climatology.  ``batch_mean`` adds the sums over B first and returns (..., C): with
+    uniform weights ``mse`` is then the reference's ``.mean(dim=(0, 2, 3))``."""
+    if sums.shape[-1] != NSUMS or sums.dim() < 3:
+        raise ValueError(f"sums must be (..., B, C, {NSUMS}), got {tuple(sums.shape)}")
+    n = float(nlon) * torch.as_tensor(w).detach().double().sum().to(sums.device)
+    if batch_mean:
+        n = n * sums.shape[-3]
+        sums = sums.sum(dim=-3)
+    n = n.to(sums.dtype)
+    se, err, ae, pa2, ta2, cross = sums.unbind(-1)
+    mse = se / n
+    # no climatology: pa2 = ta2 = 0 exactly.  (With one, both vanish only where
+    # prd = tar = clim everywhere, and 0 / 0 is NaN there too.)
+    nan = torch.full_like(se, float("nan"))
+    none = (pa2 == 0) & (ta2 == 0)
+    skill = torch.where(none, nan, 1 - se / ta2)
+    acc = torch.where(none, nan, cross / (torch.sqrt(pa2) * torch.sqrt(ta2)))
+    return Scores(mse, torch.sqrt(mse), err / n, ae / n, skill, acc)
+
+
+def mse_normalised(mse, stds):
+    """The MSE in normalised space from the raw-space ``mse`` (..., C): mse / std^2, exact
+    because the reference's normalisation is a per-channel affine (model.py:273-279)."""
+    stds = torch.as_tensor(stds).to(mse).reshape(-1)
+    if stds.numel() != mse.shape[-1]:
+        raise ValueError(f"stds must hold one value per channel ({mse.shape[-1]}), got "
+                         f"{stds.numel()}")
+    return mse / stds ** 2
+
+
+class Verifier:
+    """The sums of ``n_scored`` scored steps of a rollout of (B, C, nlat, nlon) fields, in
+    one preallocated (n_scored, B, C, 6) device tensor ``sums`` with one workspace.
+
+    ``weights`` is one of ``losses.KINDS`` ("uniform" is the reference's ``MSELoss``,
+    "cosine" the usual area weighting) or an fp32 vector of nlat weights.  ``update``
+    launches into a slot and never synchronises, so it records into a graph; a slot that
+    was never updated holds NaN."""
+
+    def __init__(self, weights, nlat, nlon, n_scored, B, C, device="cuda"):
+        if min(nlat, nlon, n_scored, B, C) < 1:
+            raise ValueError("nlat, nlon, n_scored, B and C must be >= 1")
+        self.device = _device_key(device)
+        w = _weights(weights, nlat, self.device)
+        w = N.require_device_f32(torch.as_tensor(w).detach().to(self.device), "weights")
+        if w.dim() != 1 or w.numel() != nlat:
+            raise ValueError(f"weights must hold one weight per latitude row ({nlat}), got "
+                             f"{tuple(w.shape)}")
+        self.w = w
+        self.shape = (B, C, nlat, nlon)
+        self.sums = torch.full((n_scored, B, C, NSUMS), float("nan"), dtype=torch.float32,
+                               device=self.device)
+        self._ws = workspace(B, C, nlat, nlon, self.device)
+
+    def _on_device(self, t):
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            return t.to(self.device, non_blocking=True)
+        return t
+
+    @torch.no_grad()
+    def update(self, k, y, tar, clim=None, clim_slab=None):
+        """Score the forecast ``y`` against ``tar`` (and ``clim``, as in ``field_sums``)
+        into slot ``k``.  A host ``tar`` or ``clim`` is copied with non_blocking=True."""
+        if not 0 <= k < self.sums.shape[0]:
+            raise IndexError(f"slot {k} of {self.sums.shape[0]}")
+        if tuple(y.shape) != self.shape:
+            raise ValueError(f"expected fields of shape {self.shape}, got {tuple(y.shape)}")
+        y, tar, w = _check_fields(y, self._on_device(tar), self.w)
+        clim, clim_slab = _check_clim(self._on_device(clim), clim_slab, y.shape, y.device)
+        _launch(y, tar, w, clim, clim_slab, self.sums[k], self._ws)
+
+    def scores(self, batch_mean=False) -> Scores:
+        """``finish`` of all slots: Scores of (n_scored, B, C) tensors, or (n_scored, C)."""
+        return finish(self.sums, self.w, self.shape[3], batch_mean=batch_mean)
