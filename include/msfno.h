@@ -378,6 +378,49 @@ int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, co
                       int nlon, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Ensemble verification and the (fair) CRPS: the sums behind the ensemble-mean RMSE and
+ * bias, the MAE, the spread, the spread/skill ratio, the CRPS, the fair CRPS and the rank
+ * histogram of M members against one truth (the reference has no ensemble score; the
+ * Python mirror is msfno_amd/ensemble.py).  One pass over the members and tar, all fp32
+ * in one (real) space.  Member i of slab s = (b, c) starts at
+ *   ens + i * member_stride + s * nlat * nlon
+ * (member_stride in floats, >= S * nlat * nlon, any 16-byte phase); tar is (S, nlat, nlon),
+ * w_lat (nlat).  Per slab, summed over its pixels, with dbar = (1/M) sum_i (x_i - y):
+ *   sums[s] = { se   = sum w dbar^2,   err = sum w dbar,
+ *               abs  = sum w (1/M) sum_i |x_i - y|,
+ *               gini = sum w sum_{i<j} |x_i - x_j|,
+ *               sq   = sum w sum_{i<j} (x_i - x_j)^2 }
+ *   hist[s][r] = sum w [#{i : x_i < y} == r],  r = 0..M  (strict <; hist may be NULL,
+ *               the ranks are then not formed)
+ * Every per-pixel quantity is formed from a difference x_i - y or x_i - x_j, never from
+ * the raw values or a raw mean.  CRPS = (abs - gini / M^2) / n and the fair CRPS =
+ * (abs - gini / (M (M - 1))) / n with n = nlon sum w; sq = M sum_i (x_i - xbar)^2.
+ * 2 <= M <= 32.  A latitude band passes its own rows and their weights; the sums and the
+ * histograms of the bands add up.  Deterministic as msfno_loss_sums (no atomics: integer
+ * rank counts per row, fp32 partials combined per slab in fp64 in a fixed order); every
+ * word of sums and hist is written by every call; the workspace may hold anything on
+ * entry; nothing allocates, synchronises or memsets, so the calls record into a graph.
+ *   msfno_ens_crps_backward: the gradient of L = sum_s g[s] (abs_s - kappa gini_s),
+ *     dens_i = w_lat[h] g[s] (sign(x_i - y) / M - kappa sum_{j != i} sign(x_i - x_j)),
+ *     sign(0) = 0 (what autograd gives for |.|), kappa = 1 / M^2 or 1 / (M (M - 1));
+ *     member i of dens at dens + i * dens_member_stride + s * nlat * nlon.  g (S).  The
+ *     truth takes no gradient.  No workspace.
+ * MSFNO_EINVAL for null required pointers, an extent below 1, M < 2 or a member stride
+ * shorter than a member; MSFNO_EUNSUPPORTED for M > 32; MSFNO_EWORKSPACE for a short
+ * workspace; all before any launch.  msfno_ens_workspace_size returns 0 for arguments
+ * that msfno_ens_sums refuses.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+size_t msfno_ens_workspace_size(int S, int M, int nlat, int nlon);
+int msfno_ens_sums(const float* ens, long long member_stride, const float* tar,
+                   const float* w_lat, float* sums /* (S, 5) */, float* hist /* (S, M + 1) */,
+                   int M, int S, int nlat, int nlon, void* ws, size_t ws_bytes, void* stream);
+int msfno_ens_crps_backward(const float* ens, long long member_stride, const float* tar,
+                            const float* w_lat, const float* g, float kappa, float* dens,
+                            long long dens_member_stride, int M, int S, int nlat, int nlon,
+                            void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-degree power spectrum of spherical-harmonic coefficients and its gradient: the
  * middle step of the reference's spectral losses (MSFNO/Models/losses.py:158-232,
  * spectral_l2loss_sphere, spectral_loss_sphere, h1loss_sphere; the Python mirror is

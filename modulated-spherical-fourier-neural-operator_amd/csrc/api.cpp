@@ -1574,6 +1574,39 @@ int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, co
                             (hipStream_t)stream);
 }
 
+size_t msfno_ens_workspace_size(int S, int M, int nlat, int nlon) {
+  if (S <= 0 || M < 2 || M > 32 || nlat <= 0 || nlon <= 0) return 0;
+  return ens_workspace_bytes(S, M, nlat, nlon);
+}
+
+int msfno_ens_sums(const float* ens, long long member_stride, const float* tar,
+                   const float* w_lat, float* sums, float* hist, int M, int S, int nlat,
+                   int nlon, void* ws, size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(ens && tar && w_lat && sums && ws && S > 0 && nlat > 0 && nlon > 0 && M >= 2,
+                MSFNO_EINVAL, "bad ens_sums arguments");
+  MSFNO_REQUIRE(member_stride >= (long long)S * nlat * nlon, MSFNO_EINVAL,
+                "ens_sums: member_stride is shorter than a member");
+  MSFNO_REQUIRE(M <= 32, MSFNO_EUNSUPPORTED, "ens_sums: more than 32 members");
+  MSFNO_REQUIRE(ws_bytes >= msfno_ens_workspace_size(S, M, nlat, nlon), MSFNO_EWORKSPACE,
+                "ens_sums: workspace too small");
+  return launch_ens_sums(ens, member_stride, tar, w_lat, sums, hist, M, S, nlat, nlon, ws,
+                         (hipStream_t)stream);
+}
+
+int msfno_ens_crps_backward(const float* ens, long long member_stride, const float* tar,
+                            const float* w_lat, const float* g, float kappa, float* dens,
+                            long long dens_member_stride, int M, int S, int nlat, int nlon,
+                            void* stream) {
+  MSFNO_REQUIRE(ens && tar && w_lat && g && dens && S > 0 && nlat > 0 && nlon > 0 && M >= 2,
+                MSFNO_EINVAL, "bad ens_crps_backward arguments");
+  MSFNO_REQUIRE(member_stride >= (long long)S * nlat * nlon &&
+                    dens_member_stride >= (long long)S * nlat * nlon,
+                MSFNO_EINVAL, "ens_crps_backward: a member stride is shorter than a member");
+  MSFNO_REQUIRE(M <= 32, MSFNO_EUNSUPPORTED, "ens_crps_backward: more than 32 members");
+  return launch_ens_crps_backward(ens, member_stride, tar, w_lat, g, kappa, dens,
+                                  dens_member_stride, M, S, nlat, nlon, (hipStream_t)stream);
+}
+
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on
 // the 8-byte grid
 static bool spectrum_args_ok(const void* a, const void* b, long long N, int lmax, int mmax) {

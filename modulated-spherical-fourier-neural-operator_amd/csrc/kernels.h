@@ -164,6 +164,18 @@ size_t verify_workspace_bytes(int BC, int nlat, int nlon);
 int launch_verify_sums(const float* prd, const float* tar, const float* w_lat, const float* clim,
                        const int* clim_slab, float* sums, int BC, int nlat, int nlon, void* ws,
                        hipStream_t s);
+// ---- ensemble.hip: ensemble verification sums and the CRPS gradient -------------------------
+// member i of slab s at ens + i * mstride + s * nlat * nlon (mstride in floats);
+// sums[s] = {se, err, abs, gini, sq}, hist[s][0..M] the weighted rank counts or null (see
+// ensemble.hip); 2 <= M <= 32; ws >= ens_workspace_bytes (may hold anything on entry)
+size_t ens_workspace_bytes(int S, int M, int nlat, int nlon);
+int launch_ens_sums(const float* ens, int64_t mstride, const float* tar, const float* w_lat,
+                    float* sums, float* hist, int M, int S, int nlat, int nlon, void* ws,
+                    hipStream_t s);
+// dens_i = w[h] g[s] (sign(x_i - y) / M - kappa sum_{j != i} sign(x_i - x_j))
+int launch_ens_crps_backward(const float* ens, int64_t mstride, const float* tar,
+                             const float* w_lat, const float* g, float kappa, float* dens,
+                             int64_t dstride, int M, int S, int nlat, int nlon, hipStream_t s);
 // ---- spectrum.hip: per-degree power spectrum and its gradient ----------------------------
 // coeffs (rows, mmax) complex interleaved, 8-byte aligned, rows = N * lmax:
 // power[r] = |c[r][0]|^2 + 2 sum_{m >= 1} |c[r][m]|^2

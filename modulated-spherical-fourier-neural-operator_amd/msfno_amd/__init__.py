@@ -11,5 +11,6 @@ from . import sfno  # noqa: F401
 from . import rollout  # noqa: F401
 from . import losses  # noqa: F401
 from . import verification  # noqa: F401
+from . import ensemble  # noqa: F401
 
 __version__ = "0.1.0"

@@ -146,6 +146,11 @@ SIGNATURES = [
     ("msfno_loss_backward", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     ("msfno_verify_workspace_size", _sz, [_i, _i, _i]),
     ("msfno_verify_sums", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    ("msfno_ens_workspace_size", _sz, [_i, _i, _i, _i]),
+    ("msfno_ens_sums", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz,
+                            _vp]),
+    ("msfno_ens_crps_backward", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _vp,
+                                     ctypes.c_longlong, _i, _i, _i, _i, _vp]),
     ("msfno_spectrum_power", _i, [_vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
     ("msfno_spectrum_power_backward", _i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
     ("msfno_band_partition", _i, [_i, _i, _i, _i, _ip, _ip]),

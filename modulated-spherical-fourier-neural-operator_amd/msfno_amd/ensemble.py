@@ -1,0 +1,259 @@
+"""Ensemble verification and the (fair) CRPS loss on the device.
+
+One run carries a whole ensemble in the batch dimension (FiLM takes a (B, C) modulation
+per batch element, so one replayed graph steps M members under M scenarios or M perturbed
+initial states).  The reference has no ensemble score; these are the standard ones.  One
+native pass (``msfno_ens_sums``, csrc/ensemble.hip) over the M members ``x_i`` and the
+truth ``y`` leaves five latitude-weighted sums per (batch, channel), with
+``dbar = (1/M) sum_i (x_i - y)``,
+
+    se   = sum w dbar^2                      gini = sum w sum_{i<j} |x_i - x_j|
+    err  = sum w dbar                        sq   = sum w sum_{i<j} (x_i - x_j)^2
+    abs  = sum w (1/M) sum_i |x_i - y|
+
+and the weighted rank counts ``hist[r] = sum w [#{i : x_i < y} == r]``, r = 0..M (strict
+``<``); ``finish`` turns them into scores with plain torch.  Every per-pixel quantity is
+formed from a difference (``x_i - y``, ``x_i - x_j``), never from raw values or a raw
+mean, so a 300 K field with 1 K of spread keeps its digits; ``sq = M sum_i (x_i - xbar)^2``
+gives the unbiased variance without cancellation.
+
+The sums are additive over rows: a latitude-band rank calls ``ensemble_sums`` on its own
+rows with ``w[rows]``, all-reduces the (B, C, 5) and (B, C, M + 1) results and finishes
+with the whole grid's ``w``.
+
+``EnsembleVerifier`` is the preallocated form for a rollout (one launch pair per scored
+step into a slot, nothing synchronises); ``Rollout.verify_ensemble`` drives it.
+``CRPSLoss`` is the training objective: the mean over (B, C) of
+``(abs - kappa gini) / (nlon sum w)`` with ``kappa = 1 / (M (M - 1))`` (fair) or
+``1 / M^2``, with the native gradient (``msfno_ens_crps_backward``) to the members only.
+"""
+from __future__ import annotations
+
+import math
+from collections import namedtuple
+
+import torch
+import torch.nn as nn
+
+from . import _native as N
+from .verification import _device_key, _weights
+
+NSUMS = 5
+SE, ERR, ABS, GINI, SQ = range(NSUMS)
+MAX_MEMBERS = 32
+
+EnsembleScores = namedtuple("EnsembleScores", ["mse", "rmse", "bias", "mae", "crps", "fair_crps",
+                                               "spread", "spread_skill", "rank_hist"])
+
+
+def _members(ens, name="ens"):
+    """``ens`` as fp32 device (M, B, C, H, W) with the inner four dimensions contiguous and a
+    member stride of at least one member (a view into a larger buffer stays a view;
+    anything else, an expanded member included, is copied)."""
+    if not ens.is_cuda:
+        raise ValueError(f"{name} must be a GPU (HIP) tensor; libmsfno has no CPU path")
+    if ens.dtype != torch.float32:
+        ens = ens.float()
+    inner = ens[0]
+    if not inner.is_contiguous() or (ens.shape[0] > 1 and ens.stride(0) < inner.numel()):
+        ens = ens.contiguous()
+    return ens
+
+
+def _check_members(ens, tar, w, grad_ok=False):
+    if ens.dim() != 5 or tar.dim() != 4 or ens.shape[1:] != tar.shape:
+        raise ValueError(f"ens must be (M, B, C, H, W) and tar (B, C, H, W), got "
+                         f"{tuple(ens.shape)} and {tuple(tar.shape)}")
+    M = ens.shape[0]
+    if M < 2:
+        raise ValueError(f"an ensemble has at least 2 members, got {M}")
+    if M > MAX_MEMBERS:
+        raise NotImplementedError(f"at most {MAX_MEMBERS} members, got {M}")
+    if not grad_ok:
+        for name, t in (("ens", ens), ("tar", tar), ("w", w)):
+            if t.requires_grad:
+                raise ValueError(f"{name} requires grad: the ensemble sums have no gradient; "
+                                 f"pass {name}.detach() (for training use CRPSLoss)")
+    ens = _members(ens)
+    tar = N.require_device_f32(tar, "tar")
+    w = N.require_device_f32(w, "w")
+    if w.dim() != 1 or w.numel() != ens.shape[3]:
+        raise ValueError(f"w must hold one weight per latitude row ({ens.shape[3]}), got "
+                         f"{tuple(w.shape)}")
+    if not (ens.device == tar.device == w.device):
+        raise ValueError("ens, tar and w must be on one device")
+    if ens.numel() == 0:
+        raise ValueError("empty fields")
+    return ens, tar, w
+
+
+def workspace(M: int, B: int, C: int, nlat: int, nlon: int, device) -> torch.Tensor:
+    """A workspace for ``msfno_ens_sums`` at this shape (contents do not matter)."""
+    return torch.empty(N.lib().msfno_ens_workspace_size(B * C, M, nlat, nlon),
+                       dtype=torch.uint8, device=device)
+
+
+@N.on_input_device
+def _launch(ens, tar, w, sums, hist, ws):
+    M, B, C, H, W = ens.shape
+    N.check(N.lib().msfno_ens_sums(ens.data_ptr(), ens.stride(0), tar.data_ptr(), w.data_ptr(),
+                                   sums.data_ptr(), N.ptr(hist), M, B * C, H, W, ws.data_ptr(),
+                                   ws.numel(), N.stream_of(ens.device)), "msfno_ens_sums")
+    return sums, hist
+
+
+@torch.no_grad()
+def ensemble_sums(ens, tar, w, hist=True):
+    """((B, C, 5) fp32 = {se, err, abs, gini, sq}, (B, C, M + 1) fp32 rank counts or None)
+    of the members ``ens`` (M, B, C, H, W) against ``tar`` (B, C, H, W), fp32 device fields,
+    under the latitude weights ``w`` (any fp32 device vector of length H).  The members may
+    be views into a larger buffer (any member stride).  2 <= M <= 32.  No gradient."""
+    ens, tar, w = _check_members(ens, tar, w)
+    M, B, C, H, W = ens.shape
+    sums = torch.empty(B, C, NSUMS, dtype=torch.float32, device=ens.device)
+    h = torch.empty(B, C, M + 1, dtype=torch.float32, device=ens.device) if hist else None
+    return _launch(ens, tar, w, sums, h, workspace(M, B, C, H, W, ens.device))
+
+
+def _kappa(M: int, fair: bool) -> float:
+    return 1.0 / (M * (M - 1)) if fair else 1.0 / (M * M)
+
+
+def finish(sums, hist, w, nlon, M) -> EnsembleScores:
+    """Scores from (..., 5) sums and (..., M + 1) rank counts (or None) taken under the
+    weights ``w`` of the whole grid, with n = nlon * sum(w):
+
+        mse = se / n, rmse = sqrt(mse), bias = err / n   (of the ensemble mean)
+        mae = abs / n                                    (mean over the members)
+        crps = (abs - gini / M^2) / n,  fair_crps = (abs - gini / (M (M - 1))) / n
+        spread = sqrt(sq / (M (M - 1)) / n)              (root of the mean unbiased variance)
+        spread_skill = sqrt((M + 1) / M) spread / rmse   (1 for a reliable ensemble)
+        rank_hist = hist / n                             (rows sum to 1)"""
+    if sums.shape[-1] != NSUMS:
+        raise ValueError(f"sums must be (..., {NSUMS}), got {tuple(sums.shape)}")
+    if M < 2:
+        raise ValueError(f"an ensemble has at least 2 members, got {M}")
+    if hist is not None and (hist.shape[-1] != M + 1 or hist.shape[:-1] != sums.shape[:-1]):
+        raise ValueError(f"hist must be {tuple(sums.shape[:-1]) + (M + 1,)}, got "
+                         f"{tuple(hist.shape)}")
+    n = float(nlon) * torch.as_tensor(w).detach().double().sum().to(sums.device)
+    n = n.to(sums.dtype)
+    se, err, ab, gini, sq = sums.unbind(-1)
+    mse = se / n
+    rmse = torch.sqrt(mse)
+    spread = torch.sqrt(sq / (M * (M - 1)) / n)
+    return EnsembleScores(mse, rmse, err / n, ab / n, (ab - gini / (M * M)) / n,
+                          (ab - gini / (M * (M - 1))) / n, spread,
+                          math.sqrt((M + 1) / M) * spread / rmse,
+                          None if hist is None else hist.to(sums.dtype) / n)
+
+
+class EnsembleVerifier:
+    """The sums and rank counts of ``n_scored`` scored steps of an M-member rollout of
+    (B, C, nlat, nlon) fields, in preallocated (n_scored, B, C, 5) ``sums`` and
+    (n_scored, B, C, M + 1) ``hist`` device tensors with one workspace.  ``weights`` as
+    ``verification.Verifier`` takes them.  ``update`` launches into a slot and never
+    synchronises, so it records into a graph; a slot that was never updated holds NaN."""
+
+    def __init__(self, weights, nlat, nlon, n_scored, M, B, C, device="cuda"):
+        if min(nlat, nlon, n_scored, B, C) < 1:
+            raise ValueError("nlat, nlon, n_scored, B and C must be >= 1")
+        if M < 2:
+            raise ValueError(f"an ensemble has at least 2 members, got {M}")
+        if M > MAX_MEMBERS:
+            raise NotImplementedError(f"at most {MAX_MEMBERS} members, got {M}")
+        self.device = _device_key(device)
+        w = _weights(weights, nlat, self.device)
+        w = N.require_device_f32(torch.as_tensor(w).detach().to(self.device), "weights")
+        if w.dim() != 1 or w.numel() != nlat:
+            raise ValueError(f"weights must hold one weight per latitude row ({nlat}), got "
+                             f"{tuple(w.shape)}")
+        self.w = w
+        self.M = M
+        self.shape = (M, B, C, nlat, nlon)
+        self.sums = torch.full((n_scored, B, C, NSUMS), float("nan"), dtype=torch.float32,
+                               device=self.device)
+        self.hist = torch.full((n_scored, B, C, M + 1), float("nan"), dtype=torch.float32,
+                               device=self.device)
+        self._ws = workspace(M, B, C, nlat, nlon, self.device)
+
+    @torch.no_grad()
+    def update(self, k, ens, tar):
+        """Score the members ``ens`` (M, B, C, nlat, nlon) against ``tar`` into slot ``k``.
+        A host ``tar`` is copied with non_blocking=True."""
+        if not 0 <= k < self.sums.shape[0]:
+            raise IndexError(f"slot {k} of {self.sums.shape[0]}")
+        if tuple(ens.shape) != self.shape:
+            raise ValueError(f"expected members of shape {self.shape}, got {tuple(ens.shape)}")
+        if isinstance(tar, torch.Tensor) and not tar.is_cuda:
+            tar = tar.to(self.device, non_blocking=True)
+        ens, tar, w = _check_members(ens, tar, self.w)
+        _launch(ens, tar, w, self.sums[k], self.hist[k], self._ws)
+
+    def scores(self) -> EnsembleScores:
+        """``finish`` of all slots: EnsembleScores of (n_scored, B, C) tensors and the
+        (n_scored, B, C, M + 1) rank histograms."""
+        return finish(self.sums, self.hist, self.w, self.shape[4], self.M)
+
+
+@N.on_input_device
+def _native_backward(ens, tar, w, g, kappa):
+    M, B, C, H, W = ens.shape
+    dens = torch.empty((M, B, C, H, W), dtype=torch.float32, device=ens.device)
+    N.check(N.lib().msfno_ens_crps_backward(ens.data_ptr(), ens.stride(0), tar.data_ptr(),
+                                            w.data_ptr(), g.data_ptr(), kappa, dens.data_ptr(),
+                                            dens.stride(0), M, B * C, H, W,
+                                            N.stream_of(ens.device)), "msfno_ens_crps_backward")
+    return dens
+
+
+class _CRPSSums(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ens, tar, w, kappa):
+        ctx.save_for_backward(ens, tar, w)
+        ctx.kappa = kappa
+        M, B, C, H, W = ens.shape
+        sums = torch.empty(B, C, NSUMS, dtype=torch.float32, device=ens.device)
+        _launch(ens, tar, w, sums, None, workspace(M, B, C, H, W, ens.device))
+        return sums[..., ABS] - kappa * sums[..., GINI]
+
+    @staticmethod
+    def backward(ctx, grad):
+        ens, tar, w = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        g = N.require_device_f32(grad, "grad")
+        return _native_backward(ens, tar, w, g, ctx.kappa), None, None, None
+
+
+def crps_sums(ens, tar, w, fair=True):
+    """(B, C) = abs - kappa gini, the unnormalised (fair) CRPS of ``ens`` (M, B, C, H, W)
+    against ``tar`` under the latitude weights ``w``; differentiable in ``ens``.  The
+    band-local entry: a latitude-band rank passes its rows and ``w[rows]`` and all-reduces."""
+    if tar.requires_grad:
+        raise NotImplementedError(
+            "the gradient with respect to the target is not implemented; pass tar.detach()")
+    ens, tar, w = _check_members(ens, tar, w.detach(), grad_ok=True)
+    return _CRPSSums.apply(ens, tar, w, _kappa(ens.shape[0], fair))
+
+
+class CRPSLoss(nn.Module):
+    """The mean over (B, C) of the latitude-weighted CRPS of M members (M, B, C, H, W)
+    against the truth (B, C, H, W):  (abs - kappa gini) / (W sum w), kappa = 1 / (M (M - 1))
+    (``fair``: unbiased in the ensemble size, the usual objective for ensemble fine-tuning)
+    or 1 / M^2.  ``weights`` is one of ``losses.KINDS`` or an fp32 vector of H weights."""
+
+    def __init__(self, weights="cosine", fair=True):
+        super().__init__()
+        self.weights = weights
+        self.fair = fair
+
+    def forward(self, ens, tar):
+        if ens.dim() != 5:
+            raise ValueError(f"ens must be (M, B, C, H, W), got {tuple(ens.shape)}")
+        w = _weights(self.weights, ens.shape[3], ens.device)
+        if not isinstance(w, torch.Tensor):
+            w = torch.as_tensor(w, dtype=torch.float32)
+        s = crps_sums(ens, tar, w, fair=self.fair)
+        n = (w.detach().double().sum() * ens.shape[4]).to(s.dtype)
+        return s.mean() / n

@@ -261,3 +261,47 @@ class Rollout:
                 item = (item,)
             verifier.update(i // every, y, *item)
         return verifier.scores()
+
+    def verify_ensemble(self, x0, truths, steps, every=1, weights="uniform",
+                        normalised_input=False, verifier=None):
+        """Score an ensemble rollout on the device: the batch of ``x0`` (M, C, H, W) is the
+        M members of one case (``self.film`` may differ per member), stepped together by
+        ``run(x0, steps)``; every step ``i`` where ``i % every == 0`` is scored against the
+        next item of ``truths``, a raw field (C, H, W) or (1, C, H, W) (a host tensor is
+        copied without blocking), exactly as ``verify`` pairs them.  The scored output is
+        viewed as (M, 1, C, H, W) without a copy.  Returns ``ensemble.EnsembleScores`` of
+        (n_scored, 1, C) tensors and the (n_scored, 1, C, M + 1) rank histograms under
+        ``weights`` (``ensemble.EnsembleVerifier``).  Pass a ``verifier`` of your own (built
+        with B = 1) to keep the raw sums or to reuse its buffers; its weights then apply."""
+        from . import ensemble as E
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.verify_ensemble scores whole fields; on a latitude-band rank call "
+                "ensemble.ensemble_sums on the rank's rows with w[rows], all-reduce the "
+                "(B, C, 5) sums and the (B, C, M + 1) rank counts over the ranks, then "
+                "ensemble.finish with the whole grid's w")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        if x0.dim() != 4:
+            raise ValueError(f"x0 must be (M, C, H, W), got {tuple(x0.shape)}")
+        M, C, H, W = x0.shape
+        n_scored = (steps + every - 1) // every
+        if verifier is None:
+            verifier = E.EnsembleVerifier(weights, H, W, n_scored, M, 1, C, device=x0.device)
+        elif verifier.sums.shape[0] < n_scored:
+            raise ValueError(f"verifier has {verifier.sums.shape[0]} slots, {n_scored} needed")
+        truths = iter(truths)
+        for i, y in self.run(x0, steps, normalised_input=normalised_input):
+            if i % every:
+                continue
+            try:
+                tar = next(truths)
+            except StopIteration:
+                raise ValueError(f"truths ran out at step {i}: {n_scored} scored steps need "
+                                 "one item each") from None
+            if tuple(tar.shape) not in ((C, H, W), (1, C, H, W)):
+                raise ValueError(f"a truth must be (C, H, W) or (1, C, H, W) = {(C, H, W)}, "
+                                 f"got {tuple(tar.shape)}")
+            verifier.update(i // every, y.contiguous().view(M, 1, C, H, W),
+                            tar.reshape(1, C, H, W))
+        return verifier.scores()
