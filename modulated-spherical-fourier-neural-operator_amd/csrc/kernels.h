@@ -146,6 +146,7 @@ int launch_gelu_grad_mul(float* dh, const float* pre, int64_t n, hipStream_t s);
 int launch_film_grad_reduce(const float* du, const float* x1, const float* an, const float* tn,
                             float scale, int BC, int64_t P, float* dgamma, float* dbeta,
                             hipStream_t s);
+// ---- row reductions over (S, nlat, nlon) fields on the scaffold of row_reduce.h ------------
 // ---- loss.hip: sphere-weighted loss sums and their gradient -----------------------------
 // sums[bc] = {sum_h w[h] sum_x (prd - tar)^2, sum_h w[h] sum_x tar^2}; prd, tar (BC, nlat,
 // nlon); ws >= loss_workspace_bytes (may hold anything on entry)

@@ -35,8 +35,8 @@ from collections import namedtuple
 import torch
 import torch.nn as nn
 
+from . import _fields as F
 from . import _native as N
-from .verification import _device_key, _weights
 
 NSUMS = 5
 SE, ERR, ABS, GINI, SQ = range(NSUMS)
@@ -60,31 +60,20 @@ def _members(ens, name="ens"):
     return ens
 
 
-def _check_members(ens, tar, w, grad_ok=False):
-    if ens.dim() != 5 or tar.dim() != 4 or ens.shape[1:] != tar.shape:
-        raise ValueError(f"ens must be (M, B, C, H, W) and tar (B, C, H, W), got "
-                         f"{tuple(ens.shape)} and {tuple(tar.shape)}")
-    M = ens.shape[0]
+def _check_count(M):
     if M < 2:
         raise ValueError(f"an ensemble has at least 2 members, got {M}")
     if M > MAX_MEMBERS:
         raise NotImplementedError(f"at most {MAX_MEMBERS} members, got {M}")
-    if not grad_ok:
-        for name, t in (("ens", ens), ("tar", tar), ("w", w)):
-            if t.requires_grad:
-                raise ValueError(f"{name} requires grad: the ensemble sums have no gradient; "
-                                 f"pass {name}.detach() (for training use CRPSLoss)")
-    ens = _members(ens)
-    tar = N.require_device_f32(tar, "tar")
-    w = N.require_device_f32(w, "w")
-    if w.dim() != 1 or w.numel() != ens.shape[3]:
-        raise ValueError(f"w must hold one weight per latitude row ({ens.shape[3]}), got "
-                         f"{tuple(w.shape)}")
-    if not (ens.device == tar.device == w.device):
-        raise ValueError("ens, tar and w must be on one device")
-    if ens.numel() == 0:
-        raise ValueError("empty fields")
-    return ens, tar, w
+
+
+def _check_members(ens, tar, w, grad_ok=False):
+    if ens.dim() != 5 or tar.dim() != 4 or ens.shape[1:] != tar.shape:
+        raise ValueError(f"ens must be (M, B, C, H, W) and tar (B, C, H, W), got "
+                         f"{tuple(ens.shape)} and {tuple(tar.shape)}")
+    _check_count(ens.shape[0])
+    return F.check_fields(ens, tar, w, "ens", _members,
+                          None if grad_ok else ("ensemble", "CRPSLoss"))
 
 
 def workspace(M: int, B: int, C: int, nlat: int, nlon: int, device) -> torch.Tensor:
@@ -136,8 +125,7 @@ def finish(sums, hist, w, nlon, M) -> EnsembleScores:
     if hist is not None and (hist.shape[-1] != M + 1 or hist.shape[:-1] != sums.shape[:-1]):
         raise ValueError(f"hist must be {tuple(sums.shape[:-1]) + (M + 1,)}, got "
                          f"{tuple(hist.shape)}")
-    n = float(nlon) * torch.as_tensor(w).detach().double().sum().to(sums.device)
-    n = n.to(sums.dtype)
+    n = F.grid_weight(w, nlon, sums.device).to(sums.dtype)
     se, err, ab, gini, sq = sums.unbind(-1)
     mse = se / n
     rmse = torch.sqrt(mse)
@@ -148,7 +136,7 @@ def finish(sums, hist, w, nlon, M) -> EnsembleScores:
                           None if hist is None else hist.to(sums.dtype) / n)
 
 
-class EnsembleVerifier:
+class EnsembleVerifier(F.SlotVerifier):
     """The sums and rank counts of ``n_scored`` scored steps of an M-member rollout of
     (B, C, nlat, nlon) fields, in preallocated (n_scored, B, C, 5) ``sums`` and
     (n_scored, B, C, M + 1) ``hist`` device tensors with one workspace.  ``weights`` as
@@ -156,38 +144,20 @@ class EnsembleVerifier:
     synchronises, so it records into a graph; a slot that was never updated holds NaN."""
 
     def __init__(self, weights, nlat, nlon, n_scored, M, B, C, device="cuda"):
-        if min(nlat, nlon, n_scored, B, C) < 1:
-            raise ValueError("nlat, nlon, n_scored, B and C must be >= 1")
-        if M < 2:
-            raise ValueError(f"an ensemble has at least 2 members, got {M}")
-        if M > MAX_MEMBERS:
-            raise NotImplementedError(f"at most {MAX_MEMBERS} members, got {M}")
-        self.device = _device_key(device)
-        w = _weights(weights, nlat, self.device)
-        w = N.require_device_f32(torch.as_tensor(w).detach().to(self.device), "weights")
-        if w.dim() != 1 or w.numel() != nlat:
-            raise ValueError(f"weights must hold one weight per latitude row ({nlat}), got "
-                             f"{tuple(w.shape)}")
-        self.w = w
+        _check_count(M)
+        super().__init__(weights, nlat, nlon, n_scored, B, C, device)
         self.M = M
         self.shape = (M, B, C, nlat, nlon)
-        self.sums = torch.full((n_scored, B, C, NSUMS), float("nan"), dtype=torch.float32,
-                               device=self.device)
-        self.hist = torch.full((n_scored, B, C, M + 1), float("nan"), dtype=torch.float32,
-                               device=self.device)
+        self.sums = self._alloc(NSUMS)
+        self.hist = self._alloc(M + 1)
         self._ws = workspace(M, B, C, nlat, nlon, self.device)
 
     @torch.no_grad()
     def update(self, k, ens, tar):
         """Score the members ``ens`` (M, B, C, nlat, nlon) against ``tar`` into slot ``k``.
         A host ``tar`` is copied with non_blocking=True."""
-        if not 0 <= k < self.sums.shape[0]:
-            raise IndexError(f"slot {k} of {self.sums.shape[0]}")
-        if tuple(ens.shape) != self.shape:
-            raise ValueError(f"expected members of shape {self.shape}, got {tuple(ens.shape)}")
-        if isinstance(tar, torch.Tensor) and not tar.is_cuda:
-            tar = tar.to(self.device, non_blocking=True)
-        ens, tar, w = _check_members(ens, tar, self.w)
+        self._check_slot(k, ens, "members")
+        ens, tar, w = _check_members(ens, self._on_device(tar), self.w)
         _launch(ens, tar, w, self.sums[k], self.hist[k], self._ws)
 
     def scores(self) -> EnsembleScores:
@@ -251,9 +221,8 @@ class CRPSLoss(nn.Module):
     def forward(self, ens, tar):
         if ens.dim() != 5:
             raise ValueError(f"ens must be (M, B, C, H, W), got {tuple(ens.shape)}")
-        w = _weights(self.weights, ens.shape[3], ens.device)
+        w = F.lat_weights(self.weights, ens.shape[3], ens.device)
         if not isinstance(w, torch.Tensor):
             w = torch.as_tensor(w, dtype=torch.float32)
         s = crps_sums(ens, tar, w, fair=self.fair)
-        n = (w.detach().double().sum() * ens.shape[4]).to(s.dtype)
-        return s.mean() / n
+        return s.mean() / F.grid_weight(w, ens.shape[4], s.device).to(s.dtype)

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _fields as F
 from . import _native as N
 from . import harmonics as _harmonics
 from .harmonics import quadrature
@@ -56,9 +57,7 @@ _weight_cache: dict = {}
 
 def device_weights(kind: str, nlat: int, device, eps: float = 1e-4) -> torch.Tensor:
     """fp32 device copy of ``sphere_weights``, cached per (kind, nlat, eps, device)."""
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    device = F.device_key(device)
     key = (kind, int(nlat), float(eps), device)
     w = _weight_cache.get(key)
     if w is None:
@@ -108,24 +107,12 @@ class _WeightedSums(torch.autograd.Function):
 def weighted_sums(prd: torch.Tensor, tar: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """(B, C, 2) = {num, den} of (B, C, H, W) fields under the latitude weights ``w``
     (any fp32 device vector of length H).  Differentiable in ``prd`` through ``num``."""
-    if prd.dim() != 4 or prd.shape != tar.shape:
-        raise ValueError(f"prd and tar must be (B, C, H, W) of one shape, got "
-                         f"{tuple(prd.shape)} and {tuple(tar.shape)}")
+    F.check_pair(prd, tar)
     if tar.requires_grad:
         raise NotImplementedError(
             "the gradient with respect to the target is not implemented (the reference "
             "never differentiates it, train.py:162); pass tar.detach()")
-    prd = N.require_device_f32(prd, "prd")
-    tar = N.require_device_f32(tar, "tar")
-    w = N.require_device_f32(w, "w")
-    if w.dim() != 1 or w.numel() != prd.shape[2]:
-        raise ValueError(f"w must hold one weight per latitude row ({prd.shape[2]}), got "
-                         f"{tuple(w.shape)}")
-    if not (prd.device == tar.device == w.device):
-        raise ValueError("prd, tar and w must be on one device")
-    if prd.numel() == 0:
-        raise ValueError("empty fields")
-    return _WeightedSums.apply(prd, tar, w)
+    return _WeightedSums.apply(*F.check_fields(prd, tar, w, "prd"))
 
 
 def _refuse_none(name, reduction):

@@ -25,8 +25,8 @@ from collections import namedtuple
 
 import torch
 
+from . import _fields as F
 from . import _native as N
-from . import losses as _losses
 
 NSUMS = 6
 SE, ERR, AE, PA2, TA2, CROSS = range(NSUMS)
@@ -36,17 +36,10 @@ Scores = namedtuple("Scores", ["mse", "rmse", "bias", "mae", "skill", "acc"])
 _slab_cache: dict = {}
 
 
-def _device_key(device):
-    device = torch.device(device)
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
-
-
 def _default_slabs(clim_dim, B, C, device):
     """The slab map of a (C, H, W) climatology (broadcast over the batch) or a
     (B, C, H, W) one; built on the device (no host copy), cached per (kind, B, C, device)."""
-    key = (clim_dim, B, C, _device_key(device))
+    key = (clim_dim, B, C, F.device_key(device))
     m = _slab_cache.get(key)
     if m is None:
         if clim_dim == 3:
@@ -57,31 +50,9 @@ def _default_slabs(clim_dim, B, C, device):
     return m
 
 
-def _weights(weights, nlat, device):
-    if isinstance(weights, str):
-        return _losses.device_weights(weights, nlat, device)
-    return weights
-
-
 def _check_fields(prd, tar, w):
-    if prd.dim() != 4 or prd.shape != tar.shape:
-        raise ValueError(f"prd and tar must be (B, C, H, W) of one shape, got "
-                         f"{tuple(prd.shape)} and {tuple(tar.shape)}")
-    for name, t in (("prd", prd), ("tar", tar), ("w", w)):
-        if t.requires_grad:
-            raise ValueError(f"{name} requires grad: the verification sums have no gradient; "
-                             f"pass {name}.detach() (for training use msfno_amd.losses)")
-    prd = N.require_device_f32(prd, "prd")
-    tar = N.require_device_f32(tar, "tar")
-    w = N.require_device_f32(w, "w")
-    if w.dim() != 1 or w.numel() != prd.shape[2]:
-        raise ValueError(f"w must hold one weight per latitude row ({prd.shape[2]}), got "
-                         f"{tuple(w.shape)}")
-    if not (prd.device == tar.device == w.device):
-        raise ValueError("prd, tar and w must be on one device")
-    if prd.numel() == 0:
-        raise ValueError("empty fields")
-    return prd, tar, w
+    F.check_pair(prd, tar)
+    return F.check_fields(prd, tar, w, "prd", no_grad=("verification", "msfno_amd.losses"))
 
 
 def _check_clim(clim, clim_slab, shape, device):
@@ -164,7 +135,7 @@ def finish(sums, w, nlon, batch_mean=False) -> Scores:
     uniform weights ``mse`` is then the reference's ``.mean(dim=(0, 2, 3))``."""
     if sums.shape[-1] != NSUMS or sums.dim() < 3:
         raise ValueError(f"sums must be (..., B, C, {NSUMS}), got {tuple(sums.shape)}")
-    n = float(nlon) * torch.as_tensor(w).detach().double().sum().to(sums.device)
+    n = F.grid_weight(w, nlon, sums.device)
     if batch_mean:
         n = n * sums.shape[-3]
         sums = sums.sum(dim=-3)
@@ -190,7 +161,7 @@ def mse_normalised(mse, stds):
     return mse / stds ** 2
 
 
-class Verifier:
+class Verifier(F.SlotVerifier):
     """The sums of ``n_scored`` scored steps of a rollout of (B, C, nlat, nlon) fields, in
     one preallocated (n_scored, B, C, 6) device tensor ``sums`` with one workspace.
 
@@ -200,33 +171,16 @@ class Verifier:
     was never updated holds NaN."""
 
     def __init__(self, weights, nlat, nlon, n_scored, B, C, device="cuda"):
-        if min(nlat, nlon, n_scored, B, C) < 1:
-            raise ValueError("nlat, nlon, n_scored, B and C must be >= 1")
-        self.device = _device_key(device)
-        w = _weights(weights, nlat, self.device)
-        w = N.require_device_f32(torch.as_tensor(w).detach().to(self.device), "weights")
-        if w.dim() != 1 or w.numel() != nlat:
-            raise ValueError(f"weights must hold one weight per latitude row ({nlat}), got "
-                             f"{tuple(w.shape)}")
-        self.w = w
+        super().__init__(weights, nlat, nlon, n_scored, B, C, device)
         self.shape = (B, C, nlat, nlon)
-        self.sums = torch.full((n_scored, B, C, NSUMS), float("nan"), dtype=torch.float32,
-                               device=self.device)
+        self.sums = self._alloc(NSUMS)
         self._ws = workspace(B, C, nlat, nlon, self.device)
-
-    def _on_device(self, t):
-        if isinstance(t, torch.Tensor) and not t.is_cuda:
-            return t.to(self.device, non_blocking=True)
-        return t
 
     @torch.no_grad()
     def update(self, k, y, tar, clim=None, clim_slab=None):
         """Score the forecast ``y`` against ``tar`` (and ``clim``, as in ``field_sums``)
         into slot ``k``.  A host ``tar`` or ``clim`` is copied with non_blocking=True."""
-        if not 0 <= k < self.sums.shape[0]:
-            raise IndexError(f"slot {k} of {self.sums.shape[0]}")
-        if tuple(y.shape) != self.shape:
-            raise ValueError(f"expected fields of shape {self.shape}, got {tuple(y.shape)}")
+        self._check_slot(k, y, "fields")
         y, tar, w = _check_fields(y, self._on_device(tar), self.w)
         clim, clim_slab = _check_clim(self._on_device(clim), clim_slab, y.shape, y.device)
         _launch(y, tar, w, clim, clim_slab, self.sums[k], self._ws)

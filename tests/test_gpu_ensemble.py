@@ -14,8 +14,8 @@ truth: a raw mean or raw squares would lose five digits.
   roundings, 2 (M + 1) + 1 once squared); the pair sums are one sequential chain of
   M (M - 1) / 2 non-negative terms per pixel; a lane then adds one term per pixel of its
   share of a row (nlon / lpr <= 64 for nlon <= 16384) and one weighted term per row it
-  visits (<= 64), which is loss.hip's 128-term chain, and the wave / block tree and the
-  fp64 combine are the "+ 3".  The worst ratio per case is printed.
+  visits (<= 64), which is the 128-term chain of csrc/row_reduce.h, and the wave / block
+  tree and the fp64 combine are the "+ 3".  The worst ratio per case is printed.
 Histogram: every bin within 1e-5 relative, exactly 0 where the restatement is 0 (counts are
 integers per row and wave; the weighted adds are a chain of <= 64 + 4 terms); the inputs
 have no x_i == y tie (asserted), a separate case pins strict < on deliberate ties.

@@ -7,7 +7,7 @@ a float4, slabs and views off the 16-byte grid, nlon % 4 != 0, a row wider than 
 of a workgroup, many small slabs, the real 721 x 1440 rows).
   sums: 1e-5 relative per entry -- the worst-case bound (3 + 128) 2^-24 of a 128-term
         sequential fp32 chain of non-negative terms (a lane's share of a row plus one
-        weighted add per row it visits, csrc/loss.hip), 10x inside the 1e-4 parity line;
+        weighted add per row it visits, csrc/row_reduce.h), 10x inside the 1e-4 parity line;
   dprd: 4 x 2^-24 |want| + 1e-30 per element: three fp32 roundings (coefficient,
         difference, product) on exact inputs.
 Class level: the three modules against the reference's own fp64 results

@@ -8,8 +8,8 @@ without a climatology, with one for every slab and with a mixed map (some -1, a
 batch-broadcast, a permuted stack); outputs and workspace pre-filled with NaN.
   se, ae, pa2, ta2: 1e-5 relative -- the bound tests/test_gpu_loss.py derives, (3 + 128)
         2^-24 for a 128-term sequential fp32 chain of non-negative terms; the kernel's
-        chain is loss.hip's (a lane's share of a row plus one weighted add per row it
-        visits, csrc/row_geom.h), so the bound is unchanged;
+        chain is that of the loss sums (a lane's share of a row plus one weighted add per
+        row it visits, csrc/row_reduce.h), so the bound is unchanged;
   err, cross: 1e-5 of their magnitude sums  sum w |p-t|,  sum w |(p-c)(t-c)|  (the same
         chain on signed terms), the magnitude sums from the restatement.
 Scores from GPU sums: |acc - want| <= 3e-5 (by Cauchy-Schwarz the magnitude sum of cross
