@@ -281,13 +281,15 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
 
     @N.on_input_device
     def native_backward(self, x, dout, gamma=None, beta=None, scale=1.0, need_dx=True,
-                        hidden_tap=None, params=()):
+                        hidden_tap=None, params=(), ws=None):
         """(dL/dx, dL/dgamma, dL/dbeta) for dout = dL/d(out) (msfno_block_backward_params;
         the forward is recomputed), plus a list of dL/dp for the parameters ``params``
         (--retrain-film).  dgamma / dbeta are None for an unfilmed call; dx is None unless
         need_dx.  ``hidden_tap`` (tests) receives the non-linear filter's recomputed hidden
         activations, (B, hidden, lmax, mmax) complex per layer, whose ReLU(real) masks this
-        backward applied."""
+        backward applied.  ``ws``: the caller's workspace (uint8 on x's device, holding
+        anything) in place of a fresh one; the call is still given the size this method
+        computes, so ``ws`` must be at least that long."""
         x = N.require_device_f32(x, "block input")
         dout = N.require_device_f32(dout, "block output gradient")
         B, C, H, W = x.shape
@@ -325,7 +327,11 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
         else:
             nbytes = L.msfno_block_backward_workspace_size(d, pf.handle, pi.handle, fa.handle,
                                                             ga.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        elif (ws.dtype != torch.uint8 or ws.device != x.device or ws.dim() != 1
+              or not ws.is_contiguous() or ws.numel() < nbytes):
+            raise ValueError(f"block backward: ws must be {nbytes} contiguous uint8 on {x.device}")
         N.check(L.msfno_block_backward_params(d, pf.handle, pi.handle, fa.handle, ga.handle,
                                               x.data_ptr(), N.ptr(g), N.ptr(b), float(scale),
                                               dout.data_ptr(), N.ptr(dx), N.ptr(dg), N.ptr(db),
