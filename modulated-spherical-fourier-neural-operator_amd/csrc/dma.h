@@ -88,6 +88,26 @@ __device__ __forceinline__ void glds16x6(uint64_t sbase, const uint32_t (&voff)[
       : "memory", "scc");  // s_add_u32 writes SCC
 }
 
+// the same with four pieces (the 16-KB weight slices of the x3h MLPs: one wave's share)
+template <int LDS_STEP>
+__device__ __forceinline__ void glds16x4(uint64_t sbase, const uint32_t (&voff)[4], uint32_t lds) {
+  unsigned keep;
+  sbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sbase >> 32)) << 32) |
+          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sbase);
+  lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds);
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
+      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1\n\t"
+      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1\n\t"
+      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %1\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "s"(sbase), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(lds),
+        "i"(LDS_STEP)
+      : "memory", "scc");
+}
+
 // s_waitcnt vmcnt(n) for a run-time n, rounded down to a supported immediate
 // (waiting for more than needed is safe)
 __device__ __forceinline__ void wait_vmcnt(int n) {

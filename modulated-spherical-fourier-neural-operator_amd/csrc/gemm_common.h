@@ -3,11 +3,10 @@
 // remap, GELU(erf) and the LDS-staged fused epilogue.
 #pragma once
 #include <cstdlib>
-#include "bf16x3.h"
 #include "common.h"
+#include "split_engine.h"
 
 namespace msfno {
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct GemmParams {
   const float* A;
@@ -98,7 +97,6 @@ __device__ __forceinline__ float erf_as(float x) {
 
 // the same A&S GELU on two values with packed fp32 math (v_pk_fma/mul/add_f32:
 // two lanes' worth per instruction; only rcp/exp2 stay scalar)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 v) {
   const f32x2 z = v * 0.70710678118654752440f;
   const f32x2 t0 = __builtin_elementwise_abs(z);

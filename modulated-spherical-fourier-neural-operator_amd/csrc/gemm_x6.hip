@@ -31,12 +31,6 @@
 
 namespace msfno {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 __global__ void split_a_kernel(const float* __restrict__ A, unsigned short* __restrict__ Ax, int M,
                                int K, int lda, int64_t sA, int Mp, int Kp) {
   const int z = blockIdx.y;
@@ -57,50 +51,14 @@ __global__ void split_a_kernel(const float* __restrict__ A, unsigned short* __re
   }
 }
 
-// NP planes per value: 3 = x6 (bf16 terms, six MFMAs per product), 2 = x3h (fp16
-// terms h0 = fp16(v), h1 = fp16(v - h0); a1·b0 + a0·b1 + a0·b0, three MFMAs; the
-// operands power-of-two scaled into fp16 range: p.x3_bscale per B row, the A image
-// row-scaled by the host, p.x3_rowmul undoing that per C row)
-template <int NP>
-struct X6Eng;
-template <>
-struct X6Eng<3> {
-  typedef bf16x8 frag;
-  __device__ static void split(float a, float b, uint32_t (&t)[3]) { split2(a, b, t[0], t[1], t[2]); }
-  __device__ static floatx16 prod(const frag (&a)[3], const frag (&b)[3], floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-  }
-};
-template <>
-struct X6Eng<2> {
-  typedef f16x8 frag;
-  __device__ static void split(float a, float b, uint32_t (&t)[2]) {
-    const f32x2 v = {a, b};
-    const f16x2 h0 = __builtin_convertvector(v, f16x2);
-    const f32x2 r = v - __builtin_convertvector(h0, f32x2);
-    const f16x2 h1 = __builtin_convertvector(r, f16x2);
-    t[0] = __builtin_bit_cast(uint32_t, h0);
-    t[1] = __builtin_bit_cast(uint32_t, h1);
-  }
-  __device__ static floatx16 prod(const frag (&a)[2], const frag (&b)[2], floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-    return c;
-  }
-};
-
+// NP planes per value (split_engine.h): 3 = x6, 2 = x3h (the operands power-of-two
+// scaled into fp16 range: p.x3_bscale per B row, the A image row-scaled by the host,
+// p.x3_rowmul undoing that per C row)
 // BPL: B arrives pre-split as bf16 planes (p.Bx), staged without conversion
 template <int BM, int BN, int WGM, int WGN, bool VEC, int EPI, bool BPL, int NP = 3>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6_kernel(GemmParams p) {
   static_assert(NP == 3 || !BPL, "x3h: fp32 B only");
-  typedef typename X6Eng<NP>::frag Frag;
+  typedef typename SplitEng<NP>::frag Frag;
   constexpr int BK = 16;
   constexpr int NTHR = 64 * WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN;
@@ -242,8 +200,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6_kernel(GemmParams p) {
         v.x *= bs; v.y *= bs; v.z *= bs; v.w *= bs;
       }
       uint32_t ta[NP], tb[NP];
-      X6Eng<NP>::split(v.x, v.y, ta);
-      X6Eng<NP>::split(v.z, v.w, tb);
+      SplitEng<NP>::split(v.x, v.y, ta);
+      SplitEng<NP>::split(v.z, v.w, tb);
       unsigned short* dst = Bs + buf * B_STAGE + kr * B_ROW + c4;
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl)
@@ -293,7 +251,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6_kernel(GemmParams p) {
         b[pl] = __builtin_bit_cast(Frag, v);
       }
 #pragma unroll
-      for (int i = 0; i < MT; ++i) acc[i][j] = X6Eng<NP>::prod(a[i], b, acc[i][j]);
+      for (int i = 0; i < MT; ++i) SplitEng<NP>::mma(a[i], b, acc[i][j]);
     }
   };
 
@@ -498,12 +456,7 @@ __global__ __launch_bounds__(256) void x3_image_kernel(const float* __restrict__
     __syncthreads();
   }
   mx = red[0];
-  float tau = 1.f;
-  if (mx > 0.f && isfinite(mx)) {
-    int e;
-    frexpf(mx, &e);
-    tau = ldexpf(1.f, 15 - e);
-  }
+  const float tau = row_scale(mx, 15);
   const int64_t plane = (int64_t)Mp * Kp;
   uint32_t* o = reinterpret_cast<uint32_t*>(img + (int64_t)z * 2 * plane + (int64_t)m * Kp);
   for (int kk = threadIdx.x; kk < Kp / 2; kk += 256) {
@@ -511,7 +464,7 @@ __global__ __launch_bounds__(256) void x3_image_kernel(const float* __restrict__
     const float v0 = (m < M && k < K) ? w[k] / bs[k] * tau : 0.f;
     const float v1 = (m < M && k + 1 < K) ? w[k + 1] / bs[k + 1] * tau : 0.f;
     uint32_t t[2];
-    X6Eng<2>::split(v0, v1, t);
+    SplitEng<2>::split(v0, v1, t);
     o[kk] = t[0];
     o[plane / 2 + kk] = t[1];
   }

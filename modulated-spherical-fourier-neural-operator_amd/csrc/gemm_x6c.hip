@@ -26,51 +26,9 @@
 
 namespace msfno {
 
-typedef __bf16 bf16x8c __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8c __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2c __attribute__((ext_vector_type(2)));
-typedef float f32x2c __attribute__((ext_vector_type(2)));
-typedef short s16x4c __attribute__((ext_vector_type(4)));
-typedef short s16x8c __attribute__((ext_vector_type(8)));
-
-// NP planes per value: 3 = the x6 engine (bf16 terms, six MFMAs per product), 2 = the
-// x3h engine (fp16 terms, three MFMAs; operands power-of-two scaled into fp16 range,
-// see the scale arrays of X6CParams and spec_scales_x3h_kernel)
-template <int NP>
-struct X6CEng;
-template <>
-struct X6CEng<3> {
-  typedef bf16x8c frag;
-  __device__ static void split(float a, float b, uint32_t (&t)[3]) { split2(a, b, t[0], t[1], t[2]); }
-  __device__ static floatx16 prod(const frag (&a)[3], const frag (&b)[3], floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-  }
-};
-template <>
-struct X6CEng<2> {
-  typedef f16x8c frag;
-  __device__ static void split(float a, float b, uint32_t (&t)[2]) {
-    const f32x2c v = {a, b};
-    const f16x2c h0 = __builtin_convertvector(v, f16x2c);
-    const f32x2c r = v - __builtin_convertvector(h0, f32x2c);
-    const f16x2c h1 = __builtin_convertvector(r, f16x2c);
-    t[0] = __builtin_bit_cast(uint32_t, h0);
-    t[1] = __builtin_bit_cast(uint32_t, h1);
-  }
-  __device__ static floatx16 prod(const frag (&a)[2], const frag (&b)[2], floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[0], c, 0, 0, 0);
-    return c;
-  }
-};
-
+// NP planes per value (split_engine.h): 3 = the x6 engine, 2 = the x3h engine (operands
+// power-of-two scaled into fp16 range, see the scale arrays of X6CParams and
+// spec_scales_x3h_kernel)
 constexpr int X6C_BM = 128, X6C_BN = 128, X6C_BK = 16;
 
 struct X6CParams {
@@ -153,6 +111,7 @@ __global__ void spec_scales_x3h_kernel(SpecWeightsX6p a) {
     m = red_m[0];
     nu = red_n[0];
     __syncthreads();
+    // row_scale(m, 15), spelled out (the call changes this kernel's register allocation)
     int e = 0;
     float tau = 1.f;
     if (m > 0.f && isfinite(m)) {
@@ -203,7 +162,7 @@ __global__ void spec_weights_3m_kernel(SpecWeightsX6p a) {
       v[t] = x * tau;
     }
     uint32_t t[NP];
-    X6CEng<NP>::split(v[0], v[1], t);
+    SplitEng<NP>::split(v[0], v[1], t);
     uint32_t* out = reinterpret_cast<uint32_t*>(a.out[l]) + mat * NP * n + f;
 #pragma unroll
     for (int pl = 0; pl < NP; ++pl) out[pl * n] = t[pl];
@@ -246,7 +205,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   static_assert(STAGE * 2 == (APC + BPC) * 1024, "stage = A + B pieces of 1 KB");
   // the x3h engine writes hidden planes in the tiled layout only
   static_assert(NP == 3 || !PLANES_OUT || (LAY & 2) != 0, "x3h: tiled plane output only");
-  typedef typename X6CEng<NP>::frag Frag;
+  typedef typename SplitEng<NP>::frag Frag;
   __shared__ __attribute__((aligned(16))) char lds_raw[LDS_BYTES];
   unsigned short* const ring = reinterpret_cast<unsigned short*>(lds_raw);
 
@@ -352,8 +311,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
 #pragma unroll
     for (int mat = 0; mat < 3; ++mat) {
       uint32_t ta[NP], tb[NP];
-      X6CEng<NP>::split(v[mat][0], v[mat][1], ta);
-      X6CEng<NP>::split(v[mat][2], v[mat][3], tb);
+      SplitEng<NP>::split(v[mat][0], v[mat][1], ta);
+      SplitEng<NP>::split(v[mat][2], v[mat][3], tb);
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl)
         *reinterpret_cast<uint2*>(base + (mat * NP + pl) * B_PLANE + off) = make_uint2(ta[pl], tb[pl]);
@@ -384,7 +343,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
     b_off[j] = A_ALL + br * BN + (((c >> 3) ^ (4 * (br & 3))) << 3) + (c & 7);
   }
   auto mfma_tile = [&](int st) {
-    typedef __attribute__((address_space(3))) s16x4c lds_s16x4;
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const unsigned short* base = ring + st * STAGE;
 #pragma unroll
     for (int mat = 0; mat < 3; ++mat) {
@@ -400,15 +359,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
 #pragma unroll
         for (int pl = 0; pl < NP; ++pl) {
           const unsigned short* q = base + (mat * NP + pl) * B_PLANE + b_off[j];
-          const s16x4c lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
               (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)q));
-          const s16x4c hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
               (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(q + 4 * BN)));
-          const s16x8c v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+          const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
           b[pl] = __builtin_bit_cast(Frag, v);
         }
 #pragma unroll
-        for (int i = 0; i < MT; ++i) acc[mat][i][j] = X6CEng<NP>::prod(a[i], b, acc[mat][i][j]);
+        for (int i = 0; i < MT; ++i) SplitEng<NP>::mma(a[i], b, acc[mat][i][j]);
       }
     }
   };
@@ -513,8 +472,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
         const int lr = idx / (BN / 4), c = 4 * (idx % (BN / 4));
         const float4 v = *reinterpret_cast<const float4*>(lds + lr * CS_LD + c);
         uint32_t ta[NP], tb[NP];
-        X6CEng<NP>::split(v.x, v.y, ta);
-        X6CEng<NP>::split(v.z, v.w, tb);
+        SplitEng<NP>::split(v.x, v.y, ta);
+        SplitEng<NP>::split(v.z, v.w, tb);
         const int m = m0 + lr, r = m & 15;
         unsigned short* d = Yt + ((int64_t)(m >> 4) * NMP + mat * NP) * B_PLANE + r * BN + x6c_tile_swz(r, c);
 #pragma unroll

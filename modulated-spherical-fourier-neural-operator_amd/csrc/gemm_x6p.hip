@@ -30,9 +30,6 @@
 
 namespace msfno {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef lds_void_t lds_void;
 
 constexpr int X6P_BM = 256, X6P_BN = 256, X6P_BK = 16;
@@ -275,16 +272,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_x6p_kernel(GemmParams p) {
         b[pl] = __builtin_bit_cast(bf16x8, v);
       }
 #pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        floatx16 c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][1], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][0], b[0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int i = 0; i < MT; ++i) SplitEng<3>::mma(a[i], b, acc[i][j]);
     }
   };
 
@@ -328,7 +316,6 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_x6p_kernel(GemmParams p) {
 // 64 B with the 16-B slots XORed by (m >> 2) & 3, B rows of 256 B with the 16-B
 // units XORed by 2 (r & 3) + 8 ((r >> 3) & 1): both conflict-free for the
 // ds_read_b128 / ds_read_b64_tr_b16 fragments of the 16x16x32 shape.
-typedef float floatx4q __attribute__((ext_vector_type(4)));
 constexpr int X6Q_BM = 256, X6Q_BN = 128, X6Q_BK = 32;
 
 template <int EPI>
@@ -405,7 +392,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(GemmParams p) {
     }
   };
 
-  floatx4q acc[MT][NT];
+  floatx4 acc[MT][NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -450,16 +437,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(GemmParams p) {
         b[pl] = __builtin_bit_cast(bf16x8, v);
       }
 #pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        floatx4q c = acc[i][j];
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[2], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][1], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][0], b[0], c, 0, 0, 0);
-        acc[i][j] = c;
-      }
+      for (int i = 0; i < MT; ++i) SplitEng<3>::mma(a[i], b, acc[i][j]);
     }
   };
 
@@ -477,7 +455,7 @@ __global__ __launch_bounds__(512) void gemm_x6q_kernel(GemmParams p) {
     st ^= 1;
   }
   __syncthreads();
-  gemm_epilogue<BM, BN, EPI, WGM, WGN, MT, NT, 16, floatx4q>(
+  gemm_epilogue<BM, BN, EPI, WGM, WGN, MT, NT, 16, floatx4>(
       p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C, addend, M, N, ldc, m0, n0);
 }
 

@@ -8,7 +8,7 @@
 //   inverse  A = S (K degrees), B = the table (K degrees x N latitudes), C = the slab.
 // fp32 is emulated by two fp16 terms per operand (v = v0 + v1, v0 = fp16(v),
 // v1 = fp16(v - v0)) and three fp16 MFMAs per product (a1·b0 + a0·b1 + a0·b0,
-// fp32 accumulation; Ootomo & Yokota 2022, as gemm_x6c.hip's x3h chain).  fp16's
+// fp32 accumulation; Ootomo & Yokota 2022: the x3h engine of split_engine.h).  fp16's
 // range is kept by exact power-of-two scales: every row of A by sigma_r,t per
 // k-tile t (the row's max over the tile's 32 k maps into [2^14, 2^15), found while
 // the tile is staged), every column of B by tau_n (its max maps into [2^14, 2^15):
@@ -34,27 +34,6 @@ namespace msfno {
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void x3_split(float a, float b, uint32_t& t0, uint32_t& t1) {
-  const f2v v = {a, b};
-  const h2v h0 = __builtin_convertvector(v, h2v);
-  const f2v r = v - __builtin_convertvector(h0, f2v);
-  const h2v h1 = __builtin_convertvector(r, h2v);
-  t0 = __builtin_bit_cast(uint32_t, h0);
-  t1 = __builtin_bit_cast(uint32_t, h1);
-}
-
-// 2^(s - e) for m = f 2^e, f in [0.5, 1); 1 for m = 0 or non-finite; exponent clamped
-__device__ __forceinline__ float pow2_scale(float m, int s) {
-  if (!(m > 0.f) || !isfinite(m)) return 1.f;
-  int e;
-  frexpf(m, &e);
-  return ldexpf(1.f, min(max(s - e, -100), 100));
-}
-
 // A column of a segmented (band exchange layout) operand: k -> k + block * (stride - w)
 __device__ __forceinline__ int64_t seg_k(int k, int w, int64_t stride) {
   return w ? k + (int64_t)(k / w) * (stride - w) : k;
@@ -74,7 +53,7 @@ __global__ __launch_bounds__(256) void x3d_image_kernel(const float* __restrict_
   for (int n = threadIdx.x; n < N; n += blockDim.x) {
     float m = 0.f;
     for (int k = 0; k < K; ++k) m = fmaxf(m, fabsf(B[(int64_t)k * ldb + n]));
-    const float tau = pow2_scale(m, 15);
+    const float tau = pow2_below(m, 15, 100);
     invs[d.offBs + n] = 1.f / tau;
     uint32_t* o0 = reinterpret_cast<uint32_t*>(o + (int64_t)n * Kp);
     uint32_t* o1 = reinterpret_cast<uint32_t*>(o + ((int64_t)N + n) * Kp);
@@ -82,7 +61,7 @@ __global__ __launch_bounds__(256) void x3d_image_kernel(const float* __restrict_
       const float v0 = k < K ? B[(int64_t)k * ldb + n] * tau : 0.f;
       const float v1 = k + 1 < K ? B[(int64_t)(k + 1) * ldb + n] * tau : 0.f;
       uint32_t t0, t1;
-      x3_split(v0, v1, t0, t1);
+      split2h(v0, v1, t0, t1);
       o0[k >> 1] = t0;
       o1[k >> 1] = t1;
     }
@@ -217,11 +196,11 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
       mx = fmaxf(mx, __shfl_xor(mx, 1));
       mx = fmaxf(mx, __shfl_xor(mx, 2));
       mx = fmaxf(mx, __shfl_xor(mx, 4));
-      const float sg = pow2_scale(mx, 15);
+      const float sg = pow2_below(mx, 15, 100);
       if ((idx & 7) == 0) isg_s[st][r] = 1.f / sg;
       uint32_t a0, a1, b0, b1;
-      x3_split(v[0] * sg, v[1] * sg, a0, a1);
-      x3_split(v[2] * sg, v[3] * sg, b0, b1);
+      split2h(v[0] * sg, v[1] * sg, a0, a1);
+      split2h(v[2] * sg, v[3] * sg, b0, b1);
       const int ks = kk >> 4, c = (kk >> 3) & 1, w = kk & 7;
       unsigned short* dst = base + (ks * BM + r) * 16 + 8 * (c ^ swz(r)) + w;
       *reinterpret_cast<uint2*>(dst) = make_uint2(a0, b0);
@@ -257,13 +236,13 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
         for (int r = 0; r < 16; ++r) t[i][j][r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      h8 a[MT][2], b[NT][2];
+      half8 a[MT][2], b[NT][2];
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const int row = wm * WM + i * 32 + l32;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-          a[i][pl] = *reinterpret_cast<const h8*>(base + pl * A_PL + (ks * BM + row) * 16 +
+          a[i][pl] = *reinterpret_cast<const half8*>(base + pl * A_PL + (ks * BM + row) * 16 +
                                                   8 * (half ^ swz(row)));
       }
 #pragma unroll
@@ -271,7 +250,7 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
         const int n = wn * WN + j * 32 + l32;
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-          b[j][pl] = *reinterpret_cast<const h8*>(base + 2 * A_PL + pl * B_PL + (ks * BN + n) * 16 +
+          b[j][pl] = *reinterpret_cast<const half8*>(base + 2 * A_PL + pl * B_PL + (ks * BN + n) * 16 +
                                                   8 * (half ^ swz(n)));
       }
 #pragma unroll
@@ -282,9 +261,7 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
             t[i][j][0] += (float)a[i][0][0] + (float)a[i][1][0] + (float)b[j][0][0] + (float)b[j][1][0];
             continue;
           }
-          t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][1], b[j][0], t[i][j], 0, 0, 0);
-          t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][1], t[i][j], 0, 0, 0);
-          t[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][0], b[j][0], t[i][j], 0, 0, 0);
+          SplitEng<2>::mma(a[i], b[j], t[i][j]);
         }
     }
     // acc += t / sigma (rows (r & 3) + 8 (r >> 2) + 4 half of the 32-row block)
@@ -444,17 +421,17 @@ __device__ __forceinline__ void x3r_body(const X3DParams& p, const GemmDesc& d, 
     av[ks][1] = make_float4(v[4], v[5], v[6], v[7]);
   }
   mx = fmaxf(mx, __shfl_xor(mx, 32));
-  const float sg = pow2_scale(mx, 15);
-  h8 a[KS][2];
+  const float sg = pow2_below(mx, 15, 100);
+  half8 a[KS][2];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     uint32_t t0[4], t1[4];
-    x3_split(av[ks][0].x * sg, av[ks][0].y * sg, t0[0], t1[0]);
-    x3_split(av[ks][0].z * sg, av[ks][0].w * sg, t0[1], t1[1]);
-    x3_split(av[ks][1].x * sg, av[ks][1].y * sg, t0[2], t1[2]);
-    x3_split(av[ks][1].z * sg, av[ks][1].w * sg, t0[3], t1[3]);
-    a[ks][0] = __builtin_bit_cast(h8, make_uint4(t0[0], t0[1], t0[2], t0[3]));
-    a[ks][1] = __builtin_bit_cast(h8, make_uint4(t1[0], t1[1], t1[2], t1[3]));
+    split2h(av[ks][0].x * sg, av[ks][0].y * sg, t0[0], t1[0]);
+    split2h(av[ks][0].z * sg, av[ks][0].w * sg, t0[1], t1[1]);
+    split2h(av[ks][1].x * sg, av[ks][1].y * sg, t0[2], t1[2]);
+    split2h(av[ks][1].z * sg, av[ks][1].w * sg, t0[3], t1[3]);
+    a[ks][0] = frag_cast<half8>(t0[0], t0[1], t0[2], t0[3]);
+    a[ks][1] = frag_cast<half8>(t1[0], t1[1], t1[2], t1[3]);
   }
   // 1 / sigma of the 16 rows this lane's accumulator holds: (r & 3) + 8 (r >> 2) + 4 half
   float isv[16];
@@ -482,8 +459,10 @@ __device__ __forceinline__ void x3r_body(const X3DParams& p, const GemmDesc& d, 
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int off = ks * 1024 + l32 * 32 + 16 * (half ^ x3r_swz(l32));
-      const h8 b0 = *reinterpret_cast<const h8*>(st + off);
-      const h8 b1 = *reinterpret_cast<const h8*>(st + KS * 1024 + off);
+      const half8 b0 = *reinterpret_cast<const half8*>(st + off);
+      const half8 b1 = *reinterpret_cast<const half8*>(st + KS * 1024 + off);
+      // SplitEng<2>::mma(a[ks], {b0, b1}, acc) spelled out: through the call hipcc
+      // allocates this kernel's registers differently (the only site where it does)
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ks][1], b0, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ks][0], b1, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[ks][0], b0, acc, 0, 0, 0);
@@ -539,8 +518,6 @@ __global__ __launch_bounds__(256) void legendre_x3r_kernel(X3DParams p) {
 // accumulator.  No conversion work in the kernel.
 constexpr int X3F_STAGE = 2 * (X3F_KMAX / 32) * 1024;  // bytes per stage (max Kp)
 
-typedef float f4v __attribute__((ext_vector_type(4)));
-
 template <int KS, int NST>
 __device__ __forceinline__ void x3f_body(const X3FParams& p, const GemmDesc& d, int m0, int n0,
                                          unsigned char* ring, float* isr_s) {
@@ -578,12 +555,12 @@ __device__ __forceinline__ void x3f_body(const X3FParams& p, const GemmDesc& d, 
   // B: this wave's 16 columns, lane (n = lane & 15, k = 32 ks + 8 (lane >> 4) .. + 7)
   const int col = n0 + 16 * wave + (lane & 15);
   const unsigned short* bp = p.img + d.offBx + (int64_t)min(col, N - 1) * KP + 8 * (lane >> 4);
-  h8 b[KS][2];
+  half8 b[KS][2];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
     for (int pl = 0; pl < 2; ++pl)
-      b[ks][pl] = *reinterpret_cast<const h8*>(bp + (int64_t)pl * N * KP + 32 * ks);
+      b[ks][pl] = *reinterpret_cast<const half8*>(bp + (int64_t)pl * N * KP + 32 * ks);
   const float it = p.invs[d.offBs + min(col, N - 1)];
   for (int r = tid; r < rows; r += 256) isr_s[r] = p.isr[m0 + r];
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -604,14 +581,12 @@ __device__ __forceinline__ void x3f_body(const X3FParams& p, const GemmDesc& d, 
     const unsigned char* st = ring + s * X3F_STAGE;
     const int r16 = lane & 15, kq = lane >> 4;
     const int off = r16 * 64 + 16 * (kq ^ ((r16 >> 2) & 3));
-    f4v acc = {0.f, 0.f, 0.f, 0.f};
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const h8 a0 = *reinterpret_cast<const h8*>(st + (2 * ks) * 1024 + off);
-      const h8 a1 = *reinterpret_cast<const h8*>(st + (2 * ks + 1) * 1024 + off);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b[ks][0], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b[ks][1], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b[ks][0], acc, 0, 0, 0);
+      const half8 a[2] = {*reinterpret_cast<const half8*>(st + (2 * ks) * 1024 + off),
+                          *reinterpret_cast<const half8*>(st + (2 * ks + 1) * 1024 + off)};
+      SplitEng<2>::mma(a, b[ks], acc);
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -42,8 +42,6 @@ namespace msfno {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int MF_C = 256, MF_H = 512;
 constexpr int MF_WAVES = 4, MF_PX = 32 * MF_WAVES;  // pixels per workgroup tile
 constexpr int MF_HB = MF_H / 32;                    // hidden blocks
@@ -75,11 +73,6 @@ struct MlpFusedParams {
 // physical 16-B half of logical k-half h in an A-image row m (conflict-free
 // ds_read_b128: the two halves swap on row bit 3, as in gemm_x6p's A stage)
 __device__ __forceinline__ int mf_swz(int m) { return (m >> 3) & 1; }
-
-__device__ __forceinline__ bf16x8 mf_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  const uint4 u = make_uint4(a, b, c, d);
-  return __builtin_bit_cast(bf16x8, u);
-}
 
 // ---- weight images ----------------------------------------------------------------
 // W1 (H x C fp32, row-major) -> [j][kh][pl][ks][m][16]; k = 128 kh + 16 ks + 8 h + e,
@@ -237,7 +230,7 @@ void mlp_fused_kernel(MlpFusedParams p) {
       split2(fmaf(sv[2 * e], xv[2 * e], tv[2 * e]),
              fmaf(sv[2 * e + 1], xv[2 * e + 1], tv[2 * e + 1]), t[0][e], t[1][e], t[2][e]);
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) xf[ks][pl] = mf_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+    for (int pl = 0; pl < 3; ++pl) xf[ks][pl] = frag_cast<bf16x8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
   }
   floatx16 oacc[8];  // output accumulators (C layout rows of out block ob): b2 first
 #pragma unroll
@@ -279,16 +272,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     return ring + (q % MF_NS) * MF_SLICE_ELEMS;
-  };
-
-  auto mfma6 = [](const bf16x8 (&a)[3], const bf16x8 (&b)[3], floatx16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
   };
 
   // Scheduling: every k-step is one region (sched_barrier) laid out as
@@ -345,7 +328,7 @@ void mlp_fused_kernel(MlpFusedParams p) {
           a[(ks + MF_AHEAD) % (MF_AHEAD + 1)][pl] =
               *reinterpret_cast<const bf16x8*>(slot + (pl * 8 + ks + MF_AHEAD) * 512 + a_lane);
       }
-      hacc[PAR] = mfma6(a[ks % (MF_AHEAD + 1)], xf[KH * 8 + ks], hacc[PAR]);
+      SplitEng<3>::mma(a[ks % (MF_AHEAD + 1)], xf[KH * 8 + ks], hacc[PAR]);
       if (ks == 0) refill(q);
       if constexpr (CONV) {
         if (ks & 1) conv_pair(jc, 4 * KH + (ks >> 1), PPrev{});
@@ -378,11 +361,10 @@ void mlp_fused_kernel(MlpFusedParams p) {
       }
       const int s = it & 1;
       const uint32_t (&h)[2][3][4] = hfu;
-      const bf16x8 hb[3] = {mf_frag(h[s][0][0], h[s][0][1], h[s][0][2], h[s][0][3]),
-                            mf_frag(h[s][1][0], h[s][1][1], h[s][1][2], h[s][1][3]),
-                            mf_frag(h[s][2][0], h[s][2][1], h[s][2][2], h[s][2][3])};
-      oacc[OH * 4 + (it >> 1)] =
-          mfma6(a[it % (MF_AHEAD + 1)], hb, oacc[OH * 4 + (it >> 1)]);
+      const bf16x8 hb[3] = {frag_cast<bf16x8>(h[s][0][0], h[s][0][1], h[s][0][2], h[s][0][3]),
+                            frag_cast<bf16x8>(h[s][1][0], h[s][1][1], h[s][1][2], h[s][1][3]),
+                            frag_cast<bf16x8>(h[s][2][0], h[s][2][1], h[s][2][2], h[s][2][3])};
+      SplitEng<3>::mma(a[it % (MF_AHEAD + 1)], hb, oacc[OH * 4 + (it >> 1)]);
       if (it == 0) refill(q);
       kstep_schedule(it + MF_AHEAD < 8);
     }
@@ -484,17 +466,17 @@ void mlp_fused_kernel(MlpFusedParams p) {
         if (ks + 2 < 8) load_frag(q, kind_c, ks + 2);
         const int fi = ks & 3;
         if constexpr (KIND == 0) {
-          hacc[PAR] = mfma6(af[fi], xf[SUB * 8 + ks], hacc[PAR]);
+          SplitEng<3>::mma(af[fi], xf[SUB * 8 + ks], hacc[PAR]);
           if constexpr (CONV) {
             if (ks & 1) conv_pair(jc, 4 * SUB + (ks >> 1), PPrev{});
           }
         } else {
           const int sh = ks & 1;
           const uint32_t (&h)[2][3][4] = hfu;
-          const bf16x8 hb[3] = {mf_frag(h[sh][0][0], h[sh][0][1], h[sh][0][2], h[sh][0][3]),
-                                mf_frag(h[sh][1][0], h[sh][1][1], h[sh][1][2], h[sh][1][3]),
-                                mf_frag(h[sh][2][0], h[sh][2][1], h[sh][2][2], h[sh][2][3])};
-          oacc[SUB * 4 + (ks >> 1)] = mfma6(af[fi], hb, oacc[SUB * 4 + (ks >> 1)]);
+          const bf16x8 hb[3] = {frag_cast<bf16x8>(h[sh][0][0], h[sh][0][1], h[sh][0][2], h[sh][0][3]),
+                                frag_cast<bf16x8>(h[sh][1][0], h[sh][1][1], h[sh][1][2], h[sh][1][3]),
+                                frag_cast<bf16x8>(h[sh][2][0], h[sh][2][1], h[sh][2][2], h[sh][2][3])};
+          SplitEng<3>::mma(af[fi], hb, oacc[SUB * 4 + (ks >> 1)]);
         }
         kstep_schedule(ks + 2 < 8);
         if constexpr (NEXT != 2) {

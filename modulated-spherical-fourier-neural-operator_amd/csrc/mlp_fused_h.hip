@@ -8,8 +8,9 @@
 //   a·b ~= a1·b0 + a0·b1 + a0·b0     (three fp16 MFMAs, fp32 accumulation; a1·b1 and
 //                                     the representation residuals are O(2^-22))
 //
-// (the split of Ootomo & Yokota, "Recovering single precision accuracy from Tensor
-// Cores while surpassing the FP32 theoretical peak performance", 2022).  Products of
+// (split_engine.h: split2h, SplitEng<2>; the split of Ootomo & Yokota, "Recovering
+// single precision accuracy from Tensor Cores while surpassing the FP32 theoretical
+// peak performance", 2022).  Products of
 // fp16 values are exact in fp32, so the only errors beyond an fp32 GEMM's own
 // accumulation rounding are the O(2^-22) representation terms; measured against
 // fp64 the GEMM error equals that of the fp32-MFMA and x6 engines (DESIGN.md §4,
@@ -51,11 +52,6 @@ namespace msfno {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
 constexpr int MH_C = 256, MH_H = 512;
 constexpr int MH_WAVES = 4;
 constexpr int MH_HB = MH_H / 32;                    // hidden blocks
@@ -83,35 +79,6 @@ struct MlpHParams {
   int tiles_per_field;
   uint64_t* trace;      // MSFNO_MH_TRACE: 5 words per workgroup, or null
 };
-
-// 2^(t - e) for v = f 2^e (f in [0.5, 1)): maps v below 2^t; 1 for v = 0 / non-finite
-__device__ __forceinline__ float pow2_below(float v, int t) {
-  if (!(v > 0.f) || !isfinite(v)) return 1.f;
-  int e;
-  frexpf(v, &e);
-  return ldexpf(1.f, min(max(t - e, -120), 120));
-}
-
-__host__ __device__ __forceinline__ int mh_swz(int r) { return ((r >> 2) & 1) << 1; }
-
-__host__ __device__ __forceinline__ int mh_perm(int kappa) {
-  const int g = kappa >> 3, e = kappa & 7;
-  return e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4);
-}
-
-// (a, b) -> packed fp16x2 terms h0 + h1 (RNE; v_cvt_pk_f16_f32)
-__device__ __forceinline__ void split2h(float a, float b, uint32_t& t0, uint32_t& t1) {
-  const f2v v = {a, b};
-  const half2v h0 = __builtin_convertvector(v, half2v);
-  const f2v r = v - __builtin_convertvector(h0, f2v);
-  const half2v h1 = __builtin_convertvector(r, half2v);
-  t0 = __builtin_bit_cast(uint32_t, h0);
-  t1 = __builtin_bit_cast(uint32_t, h1);
-}
-
-__device__ __forceinline__ half8 mh_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return __builtin_bit_cast(half8, make_uint4(a, b, c, d));
-}
 
 // eta_j = 2^-ceil(log2 L_j), L_j = max(||W1_j||_1, |b1_j|): L_j eta_j <= 1
 __global__ void mh_eta_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
@@ -143,12 +110,7 @@ __global__ void mh_scale_kernel(const float* __restrict__ W1, const float* __res
   const int n = first ? MH_C : MH_H;
   float m = 0.f;
   for (int k = 0; k < n; ++k) m = fmaxf(m, fabsf(first ? row[k] : row[k] / eta[k]));
-  float sc = 1.f;
-  if (m > 0.f && isfinite(m)) {
-    int e;
-    frexpf(m, &e);
-    sc = ldexpf(1.f, 15 - e);
-  }
+  const float sc = row_scale(m, 15);
   if (first) s1[r] = sc; else s2[r - MH_H] = sc;
 }
 
@@ -165,7 +127,7 @@ __global__ void mh_w1_image_kernel(const float* __restrict__ W1, const float* __
     const int kh = (int)((e >> 11) & 1);
     const int j = (int)(e >> 12);
     const int kk = 2 * kkp;
-    const int g = (kk >> 3) ^ mh_swz(r);
+    const int g = (kk >> 3) ^ mlph_swz(r);
     const int k = 128 * kh + 32 * ks + 8 * g + (kk & 7);
     const int row = 32 * j + 16 * t + r;
     const float* src = W1 + (int64_t)row * MH_C + k;
@@ -180,7 +142,7 @@ __global__ void mh_w1_image_kernel(const float* __restrict__ W1, const float* __
 }
 
 // W2' (C x H fp32, W2 diag(1 / eta)) · row scales -> [j][oh][pl][ot][r][32], hidden index
-// permuted by mh_perm
+// permuted by mlph_perm
 __global__ void mh_w2_image_kernel(const float* __restrict__ W2, const float* __restrict__ eta,
                                    const float* __restrict__ s2, unsigned short* __restrict__ img) {
   constexpr int64_t PAIRS = (int64_t)MH_HB * 2 * 8 * 16 * 16;
@@ -192,12 +154,12 @@ __global__ void mh_w2_image_kernel(const float* __restrict__ W2, const float* __
     const int oh = (int)((e >> 11) & 1);
     const int j = (int)(e >> 12);
     const int kk = 2 * kkp;
-    const int kap = 8 * ((kk >> 3) ^ mh_swz(r)) + (kk & 7);
+    const int kap = 8 * ((kk >> 3) ^ mlph_swz(r)) + (kk & 7);
     const int orow = 128 * oh + 16 * ot + r;
     const float* row = W2 + (int64_t)orow * MH_H + 32 * j;
     const float* er = eta + 32 * j;
     const float sc = s2[orow];
-    const int k0 = mh_perm(kap), k1 = mh_perm(kap + 1);
+    const int k0 = mlph_perm(kap), k1 = mlph_perm(kap + 1);
     uint32_t t0, t1;
     split2h(row[k0] / er[k0] * sc, row[k1] / er[k1] * sc, t0, t1);
     uint32_t* o = reinterpret_cast<uint32_t*>(
@@ -221,29 +183,6 @@ __device__ __forceinline__ const unsigned short* mh_slice_src(const MlpHParams& 
   return r < 2 ? p.w1img + (int64_t)(2 * j + r) * MH_SLICE
                : p.w2img + (int64_t)(2 * (j - 1) + (r - 2)) * MH_SLICE;
 }
-
-// four wave-instructions (one m0 save / restore): lane l copies 16 B from sbase +
-// voff[i] to LDS byte lds + i * LDS_STEP + 16 l (dma.h glds16x6, four pieces)
-template <int LDS_STEP>
-__device__ __forceinline__ void glds16x4(uint64_t sbase, const uint32_t (&voff)[4], uint32_t lds) {
-  unsigned keep;
-  sbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sbase >> 32)) << 32) |
-          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sbase);
-  lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds);
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %1\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "s"(sbase), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(lds),
-        "i"(LDS_STEP)
-      : "memory", "scc");
-}
-
-
 
 // The block MLP for one tile of 64 pixels (4 waves of 16; two workgroups per CU).
 // Prologue: the weight slices 0..3 go in flight by LDS-DMA; the field's range scalars
@@ -317,8 +256,8 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
   if (lane == 0) red[wave] = bm;
   __syncthreads();  // (also: the first NS slices and the x1 loads landed)
   const float Bb = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float xi = pow2_below(Bb, 14);          // |x^ xi| < 2^14
-  const float etab = pow2_below(Bb + 1.f, 14);  // |h eta_j eta_b| < 2^14
+  const float xi = pow2_below(Bb, 14, 120);          // |x^ xi| < 2^14
+  const float etab = pow2_below(Bb + 1.f, 14, 120);  // |h eta_j eta_b| < 2^14
 
   // ---- normalised x1 -> fp16x2 B fragments (k-step ks: channels 32 ks + 8 g + 0..7) ----
   const float* sc = p.scale + (int64_t)z * MH_C;
@@ -341,7 +280,7 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
       split2h(fmaf(sv[2 * e], xv[ks][2 * e], tv[2 * e]),
               fmaf(sv[2 * e + 1], xv[ks][2 * e + 1], tv[2 * e + 1]), t[0][e], t[1][e]);
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = mh_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
   }
   floatx4 oacc[16];
 #pragma unroll
@@ -367,7 +306,7 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     for (int t = 0; t < 2; ++t) hacc[a][t] = floatx4{0.f, 0.f, 0.f, 0.f};
   uint32_t hfu[2][4];  // fc2 B fragment of the converted block [plane][pair]
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mh_swz(r16));
+  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
   auto afrag = [&](const unsigned short* q) -> half8 {
     return *reinterpret_cast<const half8*>(q);
   };
@@ -387,14 +326,8 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     if (q >= 1 && q + NS - 1 < MH_NSLICE) issue(q + NS - 1);
   };
 
-  // c += a (x) b, three fp16 MFMAs
-  auto mfma3 = [](const half8 (&a)[2], const half8 (&b)[2], floatx4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);
-  };
-  // two tiles' triples interleaved (no MFMA reads the accumulator its predecessor writes;
-  // each accumulator sees the same three products in the same order as mfma3)
+  // two tiles' products interleaved (no MFMA reads the accumulator its predecessor writes;
+  // each accumulator sees the same three products in the same order as SplitEng<2>::mma)
   auto mfma3x2 = [](const half8 (&a)[2], const half8 (&b)[2], floatx4& c,
                     const half8 (&a2)[2], const half8 (&b2)[2], floatx4& c2) {
     c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);
@@ -457,7 +390,7 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
         for (int pl = 0; pl < 2; ++pl)
           a[(u + AHEAD) % (AHEAD + 1)][pl] = afrag(slot + aoff(u + AHEAD, pl));
       }
-      mfma3(a[u % (AHEAD + 1)], xf[KH * 4 + (u >> 1)], hacc[PAR][u & 1]);
+      SplitEng<2>::mma(a[u % (AHEAD + 1)], xf[KH * 4 + (u >> 1)], hacc[PAR][u & 1]);
       if (u == 0) refill(q);
       if constexpr (CONV) {
         if (u == 2 || u == 6) conv_pair(jc, 2 * KH + (u >> 2), PPrev{});
@@ -472,8 +405,8 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
   auto fc2_step = [&](const unsigned short* slot, int q, auto oh_c) {
     constexpr int OH = decltype(oh_c)::value;
     auto aoff = [&](int u, int pl) { return (pl * 8 + u) * 512 + a_lane; };
-    const half8 hb[2] = {mh_frag(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]),
-                         mh_frag(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3])};
+    const half8 hb[2] = {frag_cast<half8>(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]),
+                         frag_cast<half8>(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3])};
     half8 a[AHEAD + 2][2];  // (the pair path rotates over AHEAD + 2)
 #pragma unroll
     for (int k = 0; k < AHEAD; ++k)
@@ -500,7 +433,7 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
         for (int pl = 0; pl < 2; ++pl)
           a[(u + AHEAD) % (AHEAD + 1)][pl] = afrag(slot + aoff(u + AHEAD, pl));
       }
-      mfma3(a[u % (AHEAD + 1)], hb, oacc[OH * 8 + u]);
+      SplitEng<2>::mma(a[u % (AHEAD + 1)], hb, oacc[OH * 8 + u]);
       if (u == 0) refill(q);
     }
     }
@@ -638,12 +571,7 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
   if ((k & 63) == 0) wmax[k >> 6] = m;
   __syncthreads();
   m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  float sc = 1.f;
-  if (m > 0.f && isfinite(m)) {
-    int e;
-    frexpf(m, &e);
-    sc = ldexpf(1.f, 15 - e);
-  }
+  const float sc = row_scale(m, 15);
   if (k == 0) {
     rs[(int64_t)b * MH_C + c] = sc;
     inv_rs[(int64_t)b * MH_C + c] = 1.f / sc;
@@ -652,7 +580,7 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
   const int k0 = 2 * k;  // the pair (k0, k0 + 1): one kh, ks, 8-channel group
   const int j = c >> 5, t = (c >> 4) & 1, r = c & 15;
   const int kh = k0 >> 7, ks = (k0 >> 5) & 3, gq = (k0 >> 3) & 3;
-  const int kk = 8 * (gq ^ mh_swz(r)) + (k0 & 7);  // its stored position in the 32-wide row
+  const int kk = 8 * (gq ^ mlph_swz(r)) + (k0 & 7);  // its stored position in the 32-wide row
   uint32_t t0, t1;
   if (xsb)
     split2h(row[k0] / xsb[k0] * sc, row[k0 + 1] / xsb[k0 + 1] * sc, t0, t1);
@@ -712,7 +640,7 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
       for (int e = 0; e < 4; ++e)
         split2h(sv[2 * e] * xv[2 * e], sv[2 * e + 1] * xv[2 * e + 1], t[0][e], t[1][e]);
 #pragma unroll
-      for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = mh_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+      for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
     }
   }
   for (int i = tid; i < MH_C; i += 256) {
@@ -725,7 +653,7 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
   floatx4 oacc[16];
 #pragma unroll
   for (int ot = 0; ot < 16; ++ot) oacc[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int a_lane = r16 * 32 + 8 * (g ^ mh_swz(r16));
+  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
 
 #pragma unroll
   for (int q = 0; q < SK_NSLICE; ++q) {
@@ -751,12 +679,7 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
         for (int pl = 0; pl < 2; ++pl)
           a[(u + 2) % 3][pl] = *reinterpret_cast<const half8*>(slot + aoff(u + 2, pl));
       }
-      const half8* av = a[u % 3];
-      const half8* xb = xf[kh * 4 + (u >> 1)];
-      floatx4& c = oacc[2 * j + (u & 1)];
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[1], xb[0], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[0], xb[1], c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[0], xb[0], c, 0, 0, 0);
+      SplitEng<2>::mma(a[u % 3], xf[kh * 4 + (u >> 1)], oacc[2 * j + (u & 1)]);
       if (u == 0 && q >= 1 && q + NS - 1 < SK_NSLICE) issue(q + NS - 1);
     }
   }
@@ -925,14 +848,14 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
         for (int e = 0; e < 4; ++e)
           split2h(sv[2 * e] * xv[2 * e], sv[2 * e + 1] * xv[2 * e + 1], t[0][e], t[1][e]);
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = mh_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
       }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mh_swz(r16));
+  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
   float* const ep = epi_all + wave * 32 * SP_ERS;
   uint32_t xn[2][8][2][4];
 
@@ -998,15 +921,9 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
           for (int pl = 0; pl < 2; ++pl)
             a[(u + 2) % 3][pl] = *reinterpret_cast<const half8*>(ws + aoff(u + 2, pl));
         }
-        const half8* av = a[u % 3];
 #pragma unroll
-        for (int pg = 0; pg < 2; ++pg) {
-          const half8* xb = xf[pg][kh * 4 + (u >> 1)];
-          floatx4& c = oacc[pg][2 * j + (u & 1)];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[1], xb[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[0], xb[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(av[0], xb[0], c, 0, 0, 0);
-        }
+        for (int pg = 0; pg < 2; ++pg)
+          SplitEng<2>::mma(a[u % 3], xf[pg][kh * 4 + (u >> 1)], oacc[pg][2 * j + (u & 1)]);
         if (u == 0) {
           if (q + NS - 1 < SK_NSLICE) issue(s_cur, n + NS - 1, q + NS - 1);
           else issue(s_nxt, n + NS - 1, q + NS - 1 - SK_NSLICE);
@@ -1060,7 +977,7 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
       for (int ks = 0; ks < 8; ++ks)
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl)
-          xf[pg][ks][pl] = mh_frag(xn[pg][ks][pl][0], xn[pg][ks][pl][1], xn[pg][ks][pl][2], xn[pg][ks][pl][3]);
+          xf[pg][ks][pl] = frag_cast<half8>(xn[pg][ks][pl][0], xn[pg][ks][pl][1], xn[pg][ks][pl][2], xn[pg][ks][pl][3]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's dummy DMAs land before exit
 }
@@ -1079,7 +996,7 @@ __global__ __launch_bounds__(256) void chan_pow2_scale_kernel(const float* __res
   if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0)
-    xs[blockIdx.x] = pow2_below(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), 14);
+    xs[blockIdx.x] = pow2_below(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), 14, 120);
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 //   out = W2 · GELU(W1 · [x ; x2] + b1) (+ b2) (+ addend)
 // one launch, the hidden activation on-chip: the tiling of mlp_fused_h_kernel (16 pixels
 // per wave, 64 per workgroup, two workgroups per CU, 16x16x32 fp16 MFMAs, three per fp32
-// product; mlp_fused_h.hip has the engine and its error bound) with compile-time widths:
+// product; split_engine.h has the engine, mlp_fused_h.hip its error bound) with
+// compile-time widths:
 // KS k-steps of 32 input channels (Cin + Cin2 <= 32 KS), H hidden rows (runtime, a
 // multiple of 64) and OT output tiles of 16 channels (Cout <= 16 OT).
 //
@@ -19,7 +20,7 @@
 // input, which is what an fp32 GEMM's own rounding gives.
 //
 // Weight image: a stream of 2-KB tiles (one 16 x 32 MFMA A operand, two fp16 planes,
-// [pl][r 16][32] with the mh_swz k-group swizzle), consumed in units:
+// [pl][r 16][32] with the mlph_swz k-group swizzle), consumed in units:
 //   unit 0:        fc1 tiles of hidden block 0                   (2 KS tiles)
 //   unit j (1..HB-1): fc1 tiles of block j, then fc2 tiles of block j - 1 (2 KS + OT)
 //   unit HB:       fc2 tiles of block HB - 1                     (OT)
@@ -27,7 +28,7 @@
 // multiplied) so every slice boundary falls at a compile-time tile position.  The slices
 // stream through a four-slot LDS ring by LDS-DMA exactly as in mlp_fused_h.hip.
 // fc1 tile (ks, t) of block j: W1 rows 32 j + 16 t + r, columns 32 ks + k;
-// fc2 tile ot of block j: W2' rows 16 ot + r, hidden columns 32 j + mh_perm(k) (the C
+// fc2 tile ot of block j: W2' rows 16 ot + r, hidden columns 32 j + mlph_perm(k) (the C
 // layout of the fc1 accumulators becomes fc2's B fragment in place).
 #include "dma.h"
 #include "gemm_common.h"
@@ -44,10 +45,6 @@ namespace msfno {
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MG_TILE = 1024;   // fp16 per 2-KB tile (two 512-element planes)
@@ -64,33 +61,6 @@ __host__ __device__ constexpr int mg_unit_tile(int u, int KS, int OT) {
 }
 __host__ __device__ constexpr int mg_tiles(int HB, int KS, int OT) {
   return mg_unit_tile(HB, KS, OT) + mg_round8(OT);
-}
-
-__host__ __device__ __forceinline__ int mg_swz(int r) { return ((r >> 2) & 1) << 1; }
-__host__ __device__ __forceinline__ int mg_perm(int kappa) {
-  const int g = kappa >> 3, e = kappa & 7;
-  return e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4);
-}
-
-__device__ __forceinline__ void mg_split(float a, float b, uint32_t& t0, uint32_t& t1) {
-  const f2v v = {a, b};
-  const half2v h0 = __builtin_convertvector(v, half2v);
-  const f2v r = v - __builtin_convertvector(h0, f2v);
-  const half2v h1 = __builtin_convertvector(r, half2v);
-  t0 = __builtin_bit_cast(uint32_t, h0);
-  t1 = __builtin_bit_cast(uint32_t, h1);
-}
-
-__device__ __forceinline__ half8 mg_frag(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return __builtin_bit_cast(half8, make_uint4(a, b, c, d));
-}
-
-// 2^(t - e) for v = f 2^e (f in [0.5, 1)); 1 for v = 0 / non-finite
-__device__ __forceinline__ float mg_pow2_below(float v, int t) {
-  if (!(v > 0.f) || !isfinite(v)) return 1.f;
-  int e;
-  frexpf(v, &e);
-  return ldexpf(1.f, min(max(t - e, -120), 120));
 }
 
 template <int... I, class F>
@@ -155,12 +125,7 @@ __global__ __launch_bounds__(256) void mg_scale_kernel(
   }
   if (t != 0) return;
   m = red[0];
-  float sc = 1.f;
-  if (m > 0.f && isfinite(m)) {
-    int e;
-    frexpf(m, &e);
-    sc = ldexpf(1.f, 15 - e);
-  }
+  const float sc = row_scale(m, 15);
   if (first) { s1[r] = sc; is1[r] = 1.f / sc; }
   else { s2[r - H] = sc; is2[r - H] = 1.f / sc; }
 }
@@ -182,7 +147,7 @@ __global__ void mg_image_kernel(const float* __restrict__ W1, const float* __res
     const int kkp = (int)(f & 15), r = (int)((f >> 4) & 15);
     const int64_t tile_id = f >> 8;
     const int kk = 2 * kkp;
-    const int kap = 8 * ((kk >> 3) ^ mg_swz(r)) + (kk & 7);  // k of the stored position kk
+    const int kap = 8 * ((kk >> 3) ^ mlph_swz(r)) + (kk & 7);  // k of the stored position kk
     float v0, v1;
     int64_t tile;
     if (fc1) {
@@ -197,7 +162,7 @@ __global__ void mg_image_kernel(const float* __restrict__ W1, const float* __res
     } else {
       const int j = (int)(tile_id / OT), ot = (int)(tile_id % OT);
       const int orow = 16 * ot + r;
-      const int k0 = 32 * j + mg_perm(kap), k1 = 32 * j + mg_perm(kap + 1);
+      const int k0 = 32 * j + mlph_perm(kap), k1 = 32 * j + mlph_perm(kap + 1);
       if (orow < Cout) {
         const float sc = s2[orow];
         const float* w = W2 + (int64_t)orow * H;
@@ -210,7 +175,7 @@ __global__ void mg_image_kernel(const float* __restrict__ W1, const float* __res
                     : mg_unit_tile(j + 1, KS, OT) + (j + 1 < HB ? 2 * KS : 0) + ot;
     }
     uint32_t t0, t1;
-    mg_split(v0, v1, t0, t1);
+    split2h(v0, v1, t0, t1);
     uint32_t* o = reinterpret_cast<uint32_t*>(img + tile * MG_TILE + r * 32 + kk);
     o[0] = t0;
     o[256] = t1;  // plane 1: +512 fp16
@@ -234,27 +199,6 @@ struct MlpGParams {
   int Cin, Cin2, Cout, H, nslice, tiles_per_field;
   int tiles;            // mlp_gen_hp_kernel: tiles of 128 pixels over all fields
 };
-
-// four wave-instructions (one m0 save / restore) of a 16-KB slice: lane l copies 16 B
-// from sbase + voff[i] to LDS byte lds + i * LDS_STEP + 16 l
-template <int LDS_STEP>
-__device__ __forceinline__ void mg_glds16x4(uint64_t sbase, const uint32_t (&voff)[4], uint32_t lds) {
-  unsigned keep;
-  sbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sbase >> 32)) << 32) |
-          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sbase);
-  lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds);
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %1\n\t"
-      "s_add_u32 m0, m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, %1\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "s"(sbase), "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "s"(lds),
-        "i"(LDS_STEP)
-      : "memory", "scc");
-}
 
 // BUF: x, x2, addend and output addressed as raw buffers (32-bit lane offsets; channels
 // past Cin / Cin2 and rows past Cout fall outside the plane's range, which the buffer
@@ -296,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
   for (int i = 0; i < 4; ++i) piece_off[i] = (uint32_t)(i * W * 1024 + lane * 16);
   auto issue = [&](int q) {
     const uint64_t src = reinterpret_cast<uint64_t>(p.img + (int64_t)q * SLICE_E) + (uint64_t)wave_u * 1024;
-    mg_glds16x4<W * 1024>(src, piece_off, ring_lds + (uint32_t)((q % NS) * SLICE_E * 2 + wave_u * 1024));
+    glds16x4<W * 1024>(src, piece_off, ring_lds + (uint32_t)((q % NS) * SLICE_E * 2 + wave_u * 1024));
   };
 #pragma unroll
   for (int q = 0; q < NS; ++q)
@@ -368,8 +312,8 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(xv[ks][e]));
   m = fmaxf(m, __shfl_xor(m, 16));
   m = fmaxf(m, __shfl_xor(m, 32));
-  const float xi = mg_pow2_below(m, 14);          // |x xi| < 2^14
-  const float etap = mg_pow2_below(m + 1.f, 14);  // |h eta_j etap| < 2^14
+  const float xi = pow2_below(m, 14, 120);          // |x xi| < 2^14
+  const float etap = pow2_below(m + 1.f, 14, 120);  // |h eta_j etap| < 2^14
   const float ixi = 1.f / xi, ietap = 1.f / etap;
   half8 xf[KS][2];
 #pragma unroll
@@ -377,9 +321,9 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     uint32_t t[2][4];
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      mg_split(xv[ks][2 * e] * xi, xv[ks][2 * e + 1] * xi, t[0][e], t[1][e]);
+      split2h(xv[ks][2 * e] * xi, xv[ks][2 * e + 1] * xi, t[0][e], t[1][e]);
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = mg_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
   }
   floatx4 oacc[OT];
 #pragma unroll
@@ -422,7 +366,7 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     for (int t = 0; t < 2; ++t) hacc[a][t] = floatx4{0.f, 0.f, 0.f, 0.f};
   uint32_t hfu[2][4];  // fc2 B fragment of the converted block [plane][pair]
   half8 hb[2];
-  const int a_lane = r16 * 32 + 8 * (g ^ mg_swz(r16));
+  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
 
   // slice q landed for every wave (up to NS - 2 later slices stay in flight); the slot of
   // slice q - 1 is free and takes slice q + NS - 1
@@ -436,11 +380,6 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     if (q >= 1 && q + NS - 1 < nslice) issue(q + NS - 1);
     return ring + (q % NS) * SLICE_E;
   };
-  auto mfma3 = [](const half8 (&a)[2], const half8 (&b)[2], floatx4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);
-  };
   // pair e2 (0..3) of hidden block j in hacc[PAR]: unscale, + b1, GELU(erf), scale, split
   auto conv_pair = [&](int j, int e2, auto par_c) {
     constexpr int PAR = decltype(par_c)::value;
@@ -451,11 +390,11 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     const float2 hs = *reinterpret_cast<const float2*>(etas + row);
     f32x2 v = {fmaf(hacc[PAR][t][i], is.x * ixi, b.x), fmaf(hacc[PAR][t][i + 1], is.y * ixi, b.y)};
     v = gelu_erf2(v) * f32x2{hs.x * etap, hs.y * etap};
-    mg_split(v.x, v.y, hfu[0][e2], hfu[1][e2]);
+    split2h(v.x, v.y, hfu[0][e2], hfu[1][e2]);
   };
   auto make_hb = [&]() {
-    hb[0] = mg_frag(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]);
-    hb[1] = mg_frag(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3]);
+    hb[0] = frag_cast<half8>(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]);
+    hb[1] = frag_cast<half8>(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3]);
   };
 
   // one unit: FC1 -> fc1 tiles of block j into hacc[PAR] (converting block j - 1 from
@@ -474,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
       const half8 a[2] = {*reinterpret_cast<const half8*>(tp),
                           *reinterpret_cast<const half8*>(tp + 512)};
       if constexpr (pos < n1) {
-        mfma3(a, xf[pos >> 1], hacc[PAR][pos & 1]);
+        SplitEng<2>::mma(a, xf[pos >> 1], hacc[PAR][pos & 1]);
         if constexpr (FC2) {  // four conversions of block j - 1 spread over the fc1 tiles
           constexpr int c0 = (1 * NT1) / 5, c1 = (2 * NT1) / 5, c2 = (3 * NT1) / 5, c3 = (4 * NT1) / 5;
           if constexpr (pos == c0) conv_pair(j - 1, 0, PPrev{});
@@ -488,7 +427,7 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
           for (int t = 0; t < 2; ++t) hacc[PAR ^ 1][t] = floatx4{0.f, 0.f, 0.f, 0.f};
         }
       } else {
-        mfma3(a, hb, oacc[pos - n1]);
+        SplitEng<2>::mma(a, hb, oacc[pos - n1]);
       }
     });
   };
@@ -733,8 +672,8 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
         for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(xv[pg][ks][e]));
       m = fmaxf(m, __shfl_xor(m, 16));
       m = fmaxf(m, __shfl_xor(m, 32));
-      const float xi = mg_pow2_below(m, 14);
-      etap[pg] = mg_pow2_below(m + 1.f, 14);
+      const float xi = pow2_below(m, 14, 120);
+      etap[pg] = pow2_below(m + 1.f, 14, 120);
       ixi[pg] = 1.f / xi;
       ietap[pg] = 1.f / etap[pg];
 #pragma unroll
@@ -742,9 +681,9 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
         uint32_t t[2][4];
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          mg_split(xv[pg][ks][2 * e] * xi, xv[pg][ks][2 * e + 1] * xi, t[0][e], t[1][e]);
+          split2h(xv[pg][ks][2 * e] * xi, xv[pg][ks][2 * e + 1] * xi, t[0][e], t[1][e]);
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = mg_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
       }
     }
   };
@@ -779,13 +718,8 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
       oacc[a][pg] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mg_swz(r16));
+  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
   float* const ep = epi_all + wave * 16 * ERS;
-  auto mfma3 = [](const half8 (&a)[2], const half8 (&b)[2], floatx4& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[0], c, 0, 0, 0);
-  };
   // pair e2 of hidden block j, pixel group pg (hacc[j & 1]): unscale, + b1, GELU, scale, split
   auto conv = [&](auto jc, auto pgc, auto e2c) {
     constexpr int j = decltype(jc)::value, pg = decltype(pgc)::value, e2 = decltype(e2c)::value;
@@ -797,7 +731,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
     const floatx4& h = hacc[j & 1][pg][t];
     f32x2 v = {fmaf(h[i], is.x * ixi[pg], b.x), fmaf(h[i + 1], is.y * ixi[pg], b.y)};
     v = gelu_erf2(v) * f32x2{hs.x * etap[pg], hs.y * etap[pg]};
-    mg_split(v.x, v.y, hf[j][pg][0][e2], hf[j][pg][1][e2]);
+    split2h(v.x, v.y, hf[j][pg][0][e2], hf[j][pg][1][e2]);
   };
   // the conversions of a block: 4 pairs per pixel group, spread over the next block's tiles
   constexpr int NCONV = 4 * PG;
@@ -900,7 +834,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
         if constexpr (Q < NQ1) {  // fc1 tile f: block j, k-step ks, row half t
           constexpr int f = MG_SLICE * Q + u, j = f / NT1, i = f % NT1;
 #pragma unroll
-          for (int pg = 0; pg < PG; ++pg) mfma3(av, xf[pg][i >> 1], hacc[j & 1][pg][i & 1]);
+          for (int pg = 0; pg < PG; ++pg) SplitEng<2>::mma(av, xf[pg][i >> 1], hacc[j & 1][pg][i & 1]);
           if constexpr (j >= 1) {  // block j - 1 converted under block j's tiles
             mg_for<NCONV>([&](auto cc) {
               constexpr int c = decltype(cc)::value;
@@ -923,9 +857,9 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
           }
 #pragma unroll
           for (int pg = 0; pg < PG; ++pg) {
-            const half8 hb[2] = {mg_frag(hf[u][pg][0][0], hf[u][pg][0][1], hf[u][pg][0][2], hf[u][pg][0][3]),
-                                 mg_frag(hf[u][pg][1][0], hf[u][pg][1][1], hf[u][pg][1][2], hf[u][pg][1][3])};
-            mfma3(av, hb, oacc[ot & 1][pg]);
+            const half8 hb[2] = {frag_cast<half8>(hf[u][pg][0][0], hf[u][pg][0][1], hf[u][pg][0][2], hf[u][pg][0][3]),
+                                 frag_cast<half8>(hf[u][pg][1][0], hf[u][pg][1][1], hf[u][pg][1][2], hf[u][pg][1][3])};
+            SplitEng<2>::mma(av, hb, oacc[ot & 1][pg]);
           }
         }
         if constexpr (EPI && u == 1) {
@@ -984,8 +918,8 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
                   for (int e8 = 0; e8 < 8; ++e8) m = fmaxf(m, fabsf(xval(pg, ks, e8)));
                 m = fmaxf(m, __shfl_xor(m, 16));
                 m = fmaxf(m, __shfl_xor(m, 32));
-                const float xi = mg_pow2_below(m, 14);
-                etap[pg] = mg_pow2_below(m + 1.f, 14);
+                const float xi = pow2_below(m, 14, 120);
+                etap[pg] = pow2_below(m + 1.f, 14, 120);
                 ixi[pg] = 1.f / xi;
                 ietap[pg] = 1.f / etap[pg];
 #pragma unroll
@@ -993,9 +927,9 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
                   uint32_t t[2][4];
 #pragma unroll
                   for (int e = 0; e < 4; ++e)
-                    mg_split(xval(pg, ks, 2 * e) * xi, xval(pg, ks, 2 * e + 1) * xi, t[0][e], t[1][e]);
+                    split2h(xval(pg, ks, 2 * e) * xi, xval(pg, ks, 2 * e + 1) * xi, t[0][e], t[1][e]);
 #pragma unroll
-                  for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = mg_frag(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+                  for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
                 }
               }
               prep(std::integral_constant<int, 0>{}, so_next);

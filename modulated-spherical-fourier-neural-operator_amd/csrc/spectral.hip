@@ -8,9 +8,9 @@
 #include <cstring>
 #include <string>
 
-#include "bf16x3.h"
 #include "dma.h"
 #include "kernels.h"
+#include "split_engine.h"
 
 namespace msfno {
 
@@ -305,28 +305,6 @@ __global__ __launch_bounds__(256) void transpose_fwd_sym4_kernel(
   }
 }
 
-// x3h-plane variant of the vector-store kernel, for the register-B forward Legendre
-// (legendre_x3f): the slab as two fp16 terms per value (v = v0 + v1, v0 = fp16(v),
-// v1 = fp16(v - v0): the same 4 bytes per value as fp32), interleaved per 8 k
-// ([slab][R][ldk / 8][plane][8]: a thread's 8 values are 32 contiguous bytes) under ONE
-// power-of-two scale per channel, sigma_bc = lsig[bc] from chan_affine: a bound of the
-// whole folded slab row (|x^| <= |s| sqrt(M2) + |s mean + t| for the norm0 output,
-// the rfft scaled by 2 pi / nlon gives |X^_m| <= 2 pi max |x^|, the fold doubles it)
-// mapped into [2^14, 2^15).
-// 1 / sigma goes to isr[r] for both slab rows r of the channel.  Pads are written as
-// zeros up to ldke (Xs) and ldk - ldke (Xa), so every 16-B piece the GEMM stages
-// below its K holds finite values.
-__device__ __forceinline__ void split_h2(float a, float b, uint32_t& t0, uint32_t& t1) {
-  typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-  typedef float f2_t __attribute__((ext_vector_type(2)));
-  const f2_t v = {a, b};
-  const h2_t h0 = __builtin_convertvector(v, h2_t);
-  const f2_t r = v - __builtin_convertvector(h0, f2_t);
-  const h2_t h1 = __builtin_convertvector(r, h2_t);
-  t0 = __builtin_bit_cast(uint32_t, h0);
-  t1 = __builtin_bit_cast(uint32_t, h1);
-}
-
 // Block order of the symmetric transposes (XR): the spectra rows (mmax float2 = 2888 B at
 // 721x1440) and the slab rows start off the 128-B line grid, so two neighbouring tiles
 // share the lines at their common edge; the hardware deals blocks round-robin over the
@@ -376,6 +354,17 @@ static void fwd_sym4h_launch(const float2* Xn, unsigned short* Xp, int B, int C,
                              const float* lsig, float* isr, const int* perm, int kext,
                              hipStream_t s);
 
+// x3h-plane variant of the vector-store kernel, for the register-B forward Legendre
+// (legendre_x3f): the slab as two fp16 terms per value (v = v0 + v1, v0 = fp16(v),
+// v1 = fp16(v - v0): the same 4 bytes per value as fp32), interleaved per 8 k
+// ([slab][R][ldk / 8][plane][8]: a thread's 8 values are 32 contiguous bytes) under ONE
+// power-of-two scale per channel, sigma_bc = lsig[bc] from chan_affine: a bound of the
+// whole folded slab row (|x^| <= |s| sqrt(M2) + |s mean + t| for the norm0 output,
+// the rfft scaled by 2 pi / nlon gives |X^_m| <= 2 pi max |x^|, the fold doubles it)
+// mapped into [2^14, 2^15).
+// 1 / sigma goes to isr[r] for both slab rows r of the channel.  Pads are written as
+// zeros up to ldke (Xs) and ldk - ldke (Xa), so every 16-B piece the GEMM stages
+// below its K holds finite values.
 template <int TKx, int TMx, int XR, bool PRE>
 __global__ __launch_bounds__(256) void transpose_fwd_sym4h_kernel(
     const float2* __restrict__ Xn, unsigned short* __restrict__ Xp, int B, int C,
@@ -453,10 +442,10 @@ __global__ __launch_bounds__(256) void transpose_fwd_sym4h_kernel(
     const float4 v = *reinterpret_cast<const float4*>(tile + row * LD + 8 * kv);
     const float4 w = *reinterpret_cast<const float4*>(tile + row * LD + 8 * kv + 4);
     uint4 hi, lo;
-    split_h2(v.x, v.y, hi.x, lo.x);
-    split_h2(v.z, v.w, hi.y, lo.y);
-    split_h2(w.x, w.y, hi.z, lo.z);
-    split_h2(w.z, w.w, hi.w, lo.w);
+    split2h(v.x, v.y, hi.x, lo.x);
+    split2h(v.z, v.w, hi.y, lo.y);
+    split2h(w.x, w.y, hi.z, lo.z);
+    split2h(w.z, w.w, hi.w, lo.w);
     // interleaved planes: 8 k of the high plane, then the same 8 k of the low plane
     unsigned short* dst = Xp + 2 * ((int64_t)sl * R * g.ldk +
                                     ((int64_t)(b * 2 + ri) * C + c) * g.ldk + (h ? g.ldke : 0) + k);
