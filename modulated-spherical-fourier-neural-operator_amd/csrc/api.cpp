@@ -195,38 +195,17 @@ void prof(int stage, hipStream_t s) { g_prof.mark(stage, s); }
 // ---------------------------------------------------------------------------
 
 // side stream at the lowest priority: the skip GEMM fills what the spectral path
-// leaves (+1 % over equal priority, measured); MSFNO_SIDE_PRIO=normal|high for A/B.
-// MSFNO_SIDE_CUSTRIDE=k (A/B): the side stream runs on every k-th CU only (a CU
-// mask; k coprime with 8 spreads it over all XCDs), at normal priority.
-static hipError_t create_side_stream(hipStream_t* s, int dev) {
-  const char* pe = getenv("MSFNO_SIDE_PRIO");
+// leaves (+1 % over equal priority, measured)
+static hipError_t create_side_stream(hipStream_t* s) {
   int least = 0, greatest = 0;
   hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-  const char* ce = getenv("MSFNO_SIDE_CUSTRIDE");
-  const int custride = ce ? atoi(ce) : 0;
-  if (e == hipSuccess && custride > 1) {
-    hipDeviceProp_t prop;
-    e = hipGetDeviceProperties(&prop, dev);
-    if (e == hipSuccess) {
-      const int ncu = prop.multiProcessorCount;
-      std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-      for (int i = 0; i < ncu; i += custride) mask[(size_t)i / 32] |= 1u << (i % 32);
-      e = hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
-    }
-  } else if (e == hipSuccess) {
-    if (pe && std::string(pe) == "normal")
-      e = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    else
-      e = hipStreamCreateWithPriority(s, hipStreamNonBlocking,
-                                      (pe && std::string(pe) == "high") ? greatest : least);
-  }
+  if (e == hipSuccess) e = hipStreamCreateWithPriority(s, hipStreamNonBlocking, least);
   return e;
 }
 
 int side_ctx(std::shared_ptr<SideCtx>* out, hipStream_t caller) {
   // (read at every call: tests switch it inside one process)
-  const char* se = getenv("MSFNO_SIDE_STREAM");
-  const bool enabled = !(se && se[0] == '0');
+  const bool enabled = sw_on("MSFNO_SIDE_STREAM");
   out->reset();
   if (!enabled) return MSFNO_OK;
   // no fork while the caller's stream is being captured into a HIP graph: the
@@ -274,7 +253,7 @@ int side_ctx(std::shared_ptr<SideCtx>* out, hipStream_t caller) {
     if (cur != dev) MSFNO_CHECK_HIP(hipSetDevice(dev));
     hipError_t e = hipSuccess;
     hipStream_t& pooled = side_of_dev[dev];
-    if (!pooled) e = create_side_stream(&pooled, dev);
+    if (!pooled) e = create_side_stream(&pooled);
     c->side = pooled;
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->join, hipEventDisableTiming);
@@ -460,21 +439,14 @@ int ensure_desc(msfno_sht_plan_s* p, int R, int other_ld, int64_t ldT, hipStream
 // off, two interleaved pairs: forward 0.32 vs 0.39 ms, inverse 0.52 vs 0.55 ms for the
 // fp32-MFMA descriptor GEMM); MSFNO_LEG_X3=0 keeps the fp32 GEMM.
 bool leg_x3_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_LEG_X3");
-    if (e) return e[0] == '1' && gemm_use_x6();
-    return mlp_fused_h_env() && gemm_use_x6();
-  }();
+  static const bool on = sw_is1_or("MSFNO_LEG_X3", mlp_fused_h_env()) && gemm_use_x6();
   return on;
 }
 
 // inverse problems on the register-resident kernel (legendre_x3r) when every problem
 // fits it (K <= X3R_KMAX, N <= X3R_NMAX); MSFNO_LEG_X3R=0 keeps the tiled kernel
 static bool x3r_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_LEG_X3R");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_LEG_X3R");
   return on;
 }
 
@@ -562,10 +534,7 @@ static int build_tab3(msfno_sht_plan_s* p, int R, int64_t ldT, hipStream_t s) {
 // x3h Legendre on symmetric, unsharded blocks with norm0 (the slab planes need its
 // per-channel bound); MSFNO_LEG_X3F=0 keeps legendre_x3 on the fp32 slab.
 bool x3f_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_LEG_X3F");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_LEG_X3F");
   return on;
 }
 
@@ -632,10 +601,7 @@ int legendre_fwd_x3f(msfno_sht_plan_s* f, const unsigned short* Xp, const float*
 // matrix cores, fp32-accurate split) whenever the dense GEMMs use it;
 // MSFNO_SPEC_X6=0 keeps the fp32 3M kernel for A/B
 bool spec_use_x6() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SPEC_X6");
-    return gemm_use_x6() && !(e && e[0] == '0');
-  }();
+  static const bool on = gemm_use_x6() && sw_on("MSFNO_SPEC_X6");
   return on;
 }
 
@@ -794,10 +760,7 @@ void carve_dense_ws(Carve& cv, DenseWs& w, const msfno_block_desc* d, int B) {
 // spectral MLP as Gauss 3M complex GEMMs on the x6 engine (gemm_x6c.hip);
 // MSFNO_SPEC_3M=0 keeps the real-ified 4M x6p GEMMs for A/B
 bool spec_use_3m() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SPEC_3M");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_SPEC_3M");
   return on && spec_use_x6();
 }
 
@@ -805,11 +768,7 @@ bool spec_use_3m() {
 // per product, power-of-two scaled operands) by default; MSFNO_ENGINE=x6 or
 // MSFNO_SPEC_X3H=0 keep the x6 chain (A/B)
 bool spec_use_x3h() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SPEC_X3H");
-    if (e) return e[0] == '1';
-    return mlp_fused_h_env();
-  }();
+  static const bool on = sw_is1_or("MSFNO_SPEC_X3H", mlp_fused_h_env());
   return on && spec_use_3m();
 }
 
@@ -1258,20 +1217,13 @@ int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const
 // form measured 2.8 % faster per block (rfft 0.70 -> 0.51 ms without the 1.6 GB of
 // plane stores)
 static bool skip_planes_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SKIP_PLANES");
-    return e && e[0] == '1';
-  }();
+  static const bool on = sw_is1("MSFNO_SKIP_PLANES");
   return on;
 }
 
 // the inner skip on the x3h engine by default (MSFNO_ENGINE=x6 or MSFNO_SKIP_X3H=0 keep x6)
 bool skip_x3(const msfno_block_desc* d) {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SKIP_X3H");
-    if (e) return e[0] == '1';
-    return mlp_fused_h_env();
-  }();
+  static const bool on = sw_is1_or("MSFNO_SKIP_X3H", mlp_fused_h_env());
   return on && gemm_use_x6() && !skip_planes_env() && d->inner_skip == MSFNO_SKIP_LINEAR;
 }
 
@@ -1284,10 +1236,7 @@ bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const Blo
 // MLP, and an LDS-DMA inverse FFT whose rows tile the plane rows (P % 8 == 0);
 // MSFNO_X1_PLANES=0 keeps fp32 x1 for A/B
 bool x1_planes(const msfno_block_desc* d, const msfno_sht_plan_s* g) {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_X1_PLANES");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_X1_PLANES");
   return on && d->has_mlp && mlp_h_planes(true) && !mlp_fused(d, (int64_t)g->nlat * g->nlon) &&
          ((int64_t)g->nlat * g->nlon) % 8 == 0 && fft_c2r_planes_supported(g->fft, g->mmax);
 }
@@ -1322,10 +1271,7 @@ int run_block_mlp(const msfno_block_desc* d, const float* x1, const unsigned sho
 // MLP hidden activation in the bf16x3 plane format (x6 engine; MSFNO_H_PLANES=0
 // keeps it fp32 for A/B)
 bool mlp_h_planes(bool have_ws) {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_H_PLANES");
-    return gemm_use_x6() && !(e && e[0] == '0');
-  }();
+  static const bool on = gemm_use_x6() && sw_on("MSFNO_H_PLANES");
   return on && have_ws;
 }
 
@@ -1391,7 +1337,7 @@ int msfno_sht_plan_load_table(msfno_sht_plan_t p, const float* table, void* stre
   hipStream_t s = (hipStream_t)stream;
   // one-time setup: detect the equatorial symmetry of this table (host sync)
   int sym = 0;
-  if (!getenv("MSFNO_NO_SYM") && p->nlat >= 2) {
+  if (!sw_set("MSFNO_NO_SYM") && p->nlat >= 2) {
     int* d_flag = nullptr;
     MSFNO_CHECK_HIP(hipMalloc(&d_flag, sizeof(int)));
     int h_flag = 0;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/msfno.h"
+#include "switches.h"
 
 namespace msfno {
 
@@ -50,6 +51,19 @@ inline int launch_check(const char* what) {
     return MSFNO_EHIP;
   }
   return MSFNO_OK;
+}
+
+// multiprocessor (CU) count of the device current at the first call, 256 on failure;
+// cached for the process (it sizes the persistent grids: one workgroup per CU)
+inline int device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return cus;
 }
 
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }

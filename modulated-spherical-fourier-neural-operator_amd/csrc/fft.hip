@@ -11,7 +11,6 @@
 // pass over HBM; the inverse kernel can apply GELU and emit output-row stats.
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #include "bf16x3.h"
@@ -721,6 +720,7 @@ __global__ __launch_bounds__(64 * WV) void fft_r2c_dma_kernel(const float* __res
   // waves, which the smaller slots would allow, were slower
   constexpr int SLOT = (RB + 15) / 16 * 16;
   // NS row slots per wave: NS - 1 rows in flight while one is transformed
+  static_assert(NS == 2, "only the two-slot form is instantiated");
   extern __shared__ float2 smem[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float2* tw = smem;
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(64 * WV) void fft_r2c_dma_kernel(const float* __res
         glds16(src + min(c * 1024 + lane * 16, RB - 16), dst + c * 1024);
   };
   if (row0 < rows) issue(row0, 0);
-  if (NS > 1 && row0 + stride < rows) issue(row0 + stride, 1);
+  if (row0 + stride < rows) issue(row0 + stride, 1);
   constexpr bool PL8 = PL && N % 8 == 0;  // 16-B plane stores (8 values per lane)
   constexpr int NSP = PL8 ? 3 * ((N / 8 + 63) / 64) : (PL ? 3 * ((N / 4 + 63) / 64) : 0);
   const int nst = (mmax + 63) / 64 + (rowstats ? 1 : 0) + NSP;  // vector stores per row
@@ -748,16 +748,9 @@ __global__ __launch_bounds__(64 * WV) void fft_r2c_dma_kernel(const float* __res
   int i = 0;
   for (int64_t row = row0; row < rows; row += stride, ++i) {
     // this row's copy has landed: count what this wave issued after it (the next
-    // row's copy, if any, and the stores of the previous one or two rows)
+    // row's copy, if any, issued after the stores of the previous row)
     const bool next = row + stride < rows;
-    if constexpr (NS == 1) {  // the only slot: this row was issued after the last stores
-      wait_vmcnt(0);
-    } else if constexpr (NS == 3) {
-      wait_vmcnt((i >= 2 ? nst : 0) + (next ? NCH : 0) + (i >= 1 ? nst : 0));
-      if (row + 2 * stride < rows) issue(row + 2 * stride, sl == 0 ? 2 : sl - 1);
-    } else {  // the next row was issued after the previous row's stores
-      wait_vmcnt((i >= 1 ? nst : 0) + (next ? NCH : 0));
-    }
+    wait_vmcnt((i >= 1 ? nst : 0) + (next ? NCH : 0));
     float2* buf = reinterpret_cast<float2*>(slots + sl * SLOT);
     if constexpr (PL) {  // the raw row as bf16x3 planes, (b, c, lat) of row = (b*C + c)*nlat + lat
       const int64_t bc = row / pp.nlat, lat = row - bc * pp.nlat;
@@ -814,18 +807,10 @@ __global__ __launch_bounds__(64 * WV) void fft_r2c_dma_kernel(const float* __res
     for (int k = lane; k < mmax; k += 64) o[k] = bin(k);
 
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if constexpr (NS == 1) {
-      // every read of the slot has returned: refill it with the next row
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (next) issue(row + stride, 0);
-    } else if constexpr (NS == 3) {
-      sl = sl == 2 ? 0 : sl + 1;
-    } else {
-      // every read of this slot has returned: refill it with the row after next
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (row + 2 * stride < rows) issue(row + 2 * stride, sl);
-      sl ^= 1;
-    }
+    // every read of this slot has returned: refill it with the row after next
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (row + 2 * stride < rows) issue(row + 2 * stride, sl);
+    sl ^= 1;
   }
 }
 
@@ -1104,27 +1089,11 @@ using FFT32 = FixedFFT<4, 4>;             // nlon 32
 // LDS-DMA row kernels for compiled codelets (MSFNO_FFT_DMA=0: register-prefetch
 // kernels, kept for A/B)
 static bool use_fft_dma() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_FFT_DMA");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_FFT_DMA");
   return on;
 }
 
 static int set_lds_limit(const void* fn, size_t lds);
-
-// persistent grid of the DMA row kernels: one workgroup per CU
-static int64_t dma_grid() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
 
 template <class CL>
 static int launch_r2c(const FFTArgs& a, const float* x, float2* out, float2* rowstats,
@@ -1132,23 +1101,14 @@ static int launch_r2c(const FFTArgs& a, const float* x, float2* out, float2* row
                       const C2RPlanes* planes) {
   if constexpr (CL::H > 0) {
     if (use_fft_dma() && (2 * CL::H) % 8 == 0 && mmax <= CL::H + 1) {
-      // waves x row slots per workgroup, one workgroup per CU: 12 x 2 (one row in
-      // flight, 12 waves) measured 4 % faster than 8 x 3 (two rows in flight, 8
-      // waves) at 721 x 1440 and 5 x 2 (two workgroups) slower; the row FFT is
-      // latency bound, waves per CU beat rows in flight.  MSFNO_R2C_CFG=8x3|5x2 (A/B)
-      static const int cfg = [] {
-        const char* e = getenv("MSFNO_R2C_CFG");
-        if (e && std::string(e) == "8x3") return 0;
-        if (e && std::string(e) == "5x2") return 2;
-        if (e && std::string(e) == "16x1") return 3;
-        return 1;
-      }();
+      // 12 waves x 2 row slots per workgroup (one row in flight), one workgroup per CU:
+      // the row FFT is latency bound, waves per CU beat rows in flight (DESIGN.md §9b,
+      // "Retired in round 8": 8 x 3, 5 x 2 and 16 x 1 were slower)
       const size_t slot = (size_t)(2 * CL::H * 4 + 15) / 16 * 16;  // = the kernel's SLOT
       auto go = [&](auto kern, int WV, int NS) -> int {
         const size_t lds = (size_t)(2 * CL::H + 2) * sizeof(float2) + WV * NS * slot;
         MSFNO_REQUIRE(lds <= 160 * 1024, MSFNO_EUNSUPPORTED, "nlon too large for the LDS FFT");
-        const int64_t grid =
-            std::min<int64_t>(cdiv(rows, WV), dma_grid() * (WV == 5 ? 2 : 1));  // WGs per CU
+        const int64_t grid = std::min<int64_t>(cdiv(rows, WV), device_cus());
         MSFNO_TRY(set_lds_limit(reinterpret_cast<const void*>(kern), lds));
         C2RPlanes pp{};
         if (planes) pp = *planes;
@@ -1156,17 +1116,8 @@ static int launch_r2c(const FFTArgs& a, const float* x, float2* out, float2* row
                            rows, mmax, scale, a, pp);
         return launch_check("fft_r2c_dma");
       };
-      if (cfg == 1)
-        return planes ? go(fft_r2c_dma_kernel<CL, 12, true, 2>, 12, 2)
-                      : go(fft_r2c_dma_kernel<CL, 12, false, 2>, 12, 2);
-      if (cfg == 2)
-        return planes ? go(fft_r2c_dma_kernel<CL, 5, true, 2>, 5, 2)
-                      : go(fft_r2c_dma_kernel<CL, 5, false, 2>, 5, 2);
-      if (cfg == 3)
-        return planes ? go(fft_r2c_dma_kernel<CL, 16, true, 1>, 16, 1)
-                      : go(fft_r2c_dma_kernel<CL, 16, false, 1>, 16, 1);
-      return planes ? go(fft_r2c_dma_kernel<CL, 8, true>, 8, 3)
-                    : go(fft_r2c_dma_kernel<CL, 8, false>, 8, 3);
+      return planes ? go(fft_r2c_dma_kernel<CL, 12, true, 2>, 12, 2)
+                    : go(fft_r2c_dma_kernel<CL, 12, false, 2>, 12, 2);
     }
   }
   MSFNO_REQUIRE(!planes, MSFNO_EUNSUPPORTED, "r2c plane output needs the LDS-DMA row FFT");
@@ -1178,10 +1129,7 @@ static int launch_r2c(const FFTArgs& a, const float* x, float2* out, float2* row
 }
 
 static bool c2r_swz() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_C2R_SWZ");
-    return e && e[0] == '1';
-  }();
+  static const bool on = sw_is1("MSFNO_C2R_SWZ");
   return on;
 }
 
@@ -1198,10 +1146,7 @@ static int launch_c2r(const FFTArgs& a, const float2* in, float* x, const float*
       // one row ahead, 4-wave workgroups, as many per CU as the LDS holds
       // skip rows through registers (no LDS slot): 16 waves per CU instead of 10,
       // irfft 0.86 -> 0.74 ms at 721 x 1440.  MSFNO_C2R_AREG=0 stages them by LDS-DMA
-      static const bool areg = [] {
-        const char* e = getenv("MSFNO_C2R_AREG");
-        return !(e && e[0] == '0');
-      }();
+      static const bool areg = sw_on("MSFNO_C2R_AREG");
       // LDS per wave: row + Yn slot (+ the skip-row slot of the LDS-DMA variants)
       const size_t per_reg = (size_t)rb + ncy * 1024;
       const size_t per = per_reg + (addsrc ? nca * 1024 : 0);
@@ -1212,7 +1157,7 @@ static int launch_c2r(const FFTArgs& a, const float2* in, float* x, const float*
         const size_t lds = tw + WV * pw;
         MSFNO_TRY(set_lds_limit(reinterpret_cast<const void*>(kern), lds));
         const int wgs = WV == 4 ? wg_cu : (int)std::max<size_t>(1, (160 * 1024) / lds);
-        const int64_t grid = std::min<int64_t>(cdiv(rows, WV), dma_grid() * wgs);
+        const int64_t grid = std::min<int64_t>(cdiv(rows, WV), (int64_t)device_cus() * wgs);
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * WV), lds, s, in, x, addsrc,
                            rowstats, rows, mmax, act, ncy, a, pp);
         return MSFNO_OK;
@@ -1220,10 +1165,7 @@ static int launch_c2r(const FFTArgs& a, const float2* in, float* x, const float*
       // block path (skip add + planes): one 10-wave workgroup per CU when the LDS holds
       // it (one twiddle copy per CU instead of two): 3 % faster than two 4-wave ones at
       // 721 x 1440.  MSFNO_C2R_WV=4 keeps the 4-wave workgroups (A/B)
-      static const bool wide = [] {
-        const char* e = getenv("MSFNO_C2R_WV");
-        return !(e && atoi(e) == 4);
-      }();
+      static const bool wide = sw_int("MSFNO_C2R_WV", 10) != 4;
       if (planes && addsrc && areg && tw + 16 * per_reg <= 160 * 1024)
         MSFNO_TRY(go(fft_c2r_dma_kernel<CL, true, 16, 1, true, true>, 16, per_reg));
       else if (planes && addsrc && wide && tw + 10 * per <= 160 * 1024)

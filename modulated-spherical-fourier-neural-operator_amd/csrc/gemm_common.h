@@ -2,7 +2,6 @@
 // fp32-accurate 6-term bf16 split): kernel parameters, the XCD-aware tile
 // remap, GELU(erf) and the LDS-staged fused epilogue.
 #pragma once
-#include <cstdlib>
 #include "common.h"
 #include "split_engine.h"
 
@@ -133,10 +132,7 @@ __device__ __forceinline__ float gelu_erf(float v) {
 
 // 16-B plane stores in the epilogue (MSFNO_CX16=0: 8-B stores, for A/B)
 inline bool cx16_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_CX16");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_CX16");
   return on;
 }
 

@@ -23,9 +23,7 @@
 //   B: [plane][k][BN + 32] (row-major as in HBM; +64 B per row makes the
 //      transposed fragment reads conflict free), read with ds_read_b64_tr_b16
 //      (4 k x 16 n per 16-lane group, delivered k-contiguous per lane).
-#include <cstdlib>
 #include <type_traits>
-#include <string>
 
 #include "gemm_common.h"
 
@@ -293,10 +291,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6_kernel(GemmParams p) {
 // ---- host ---------------------------------------------------------------------
 
 bool gemm_use_x6() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_GEMM");
-    return !(e && std::string(e) == "f32");
-  }();
+  static const bool on = !sw_eq("MSFNO_GEMM", "f32");
   return on;
 }
 
@@ -314,7 +309,7 @@ static GemmTile x6_tile(int M, int N, int batch) {
 }
 
 size_t gemm_x6_workspace(int M, int K, int batch) {
-  // k padded to 32: the same buffers also hold gemm_x6p's 32-deep x6q A image
+  // k padded to 32 (the size gemm_x6p_workspace also reserves)
   const int64_t Mp = round_up(M, 256), Kp = round_up(K, 32);
   return (size_t)round_up(3 * Mp * Kp * 2 * (int64_t)batch, 256);
 }

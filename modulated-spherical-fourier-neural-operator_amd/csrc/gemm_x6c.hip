@@ -19,7 +19,6 @@
 // wave 32 x 64 with three accumulator sets (P1, P2, P3).  Stage (72 KB) = A: 3
 // matrices x 3 planes x [128][16] + B: 3 x 3 x [16][128]; two stages, one k-tile
 // in flight (LDS-DMA, dma.h).  LDS swizzles as in gemm_x6p_kernel.
-#include <cstdlib>
 
 #include "dma.h"
 #include "gemm_common.h"
@@ -737,10 +736,7 @@ int gemm_x3c(const unsigned short* Aw, int co, int ci, const float* Sin, int ldS
   // hidden layers 0.65 vs 0.54 ms in-block, the output layer no faster once it is timed
   // beside the same side-stream skip: 0.293 ms with 64 rows in profiles/r06_v vs 0.292
   // with 128 in profiles/r06_t/ab_bm64.txt)
-  static const int bm64_on = [] {
-    const char* e = getenv("MSFNO_X3C_BM64");
-    return e ? atoi(e) : 1;
-  }();
+  static const int bm64_on = sw_int("MSFNO_X3C_BM64", 1);
   if (!Sin && bm64_on && ((int64_t)p.tiles_m * p.tiles_n * B < 2 * 256 || bm64_on == 2)) {
     p.tiles_m = p.Mp / 64;
     const dim3 g64(p.tiles_m * p.tiles_n, 1, B);
@@ -754,10 +750,7 @@ int gemm_x3c(const unsigned short* Aw, int co, int ci, const float* Sin, int ldS
   // fp32 staging needs 512 threads), two stages, two workgroups per CU: config 3 131.7 /
   // 132.3 / 132.1 vs 131.3 / 131.8 / 131.5 steps/s (three interleaved pairs,
   // profiles/r06_ac; MSFNO_X3C_L0_BM64=0 keeps the 128-row tiles)
-  static const bool l0_bm64 = [] {
-    const char* e = getenv("MSFNO_X3C_L0_BM64");
-    return !(e && e[0] == '0');
-  }();
+  static const bool l0_bm64 = sw_on("MSFNO_X3C_L0_BM64");
   if (Sin && l0_bm64 && bm64_on && (int64_t)p.tiles_m * p.tiles_n * B < 2 * 256) {
     p.tiles_m = p.Mp / 64;
     const dim3 g64(p.tiles_m * p.tiles_n, 1, B);

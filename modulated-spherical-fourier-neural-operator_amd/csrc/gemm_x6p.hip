@@ -22,9 +22,6 @@
 // swizzles are applied on the global source address.
 // A (weights) is split once per call into [batch][plane][k-tile][Mp][16] so
 // that every 1-KB piece is one contiguous run in memory.
-#include <cstdlib>
-#include <string>
-
 #include "dma.h"
 #include "gemm_common.h"
 
@@ -131,11 +128,11 @@ __global__ void split_planes_kernel(const float* __restrict__ x, unsigned short*
 template <int EPI, int NSTAGE = 3, int WAVES = 8, int BNT = 256>
 __global__ __launch_bounds__(64 * WAVES) void gemm_x6p_kernel(GemmParams p) {
   constexpr int BM = X6P_BM, BN = BNT, BK = X6P_BK;
-  // 256 x 256 tiles: 8 waves as 4 x 2 (wave 64 x 128), or 4 waves as 2 x 2 (wave
-  // 128 x 128, 256 accumulator registers: one wave per SIMD);
-  // 256 x 128 tiles: 4 waves as 4 x 1 (wave 64 x 128), 72-KB ring: two workgroups per
-  // CU, so one's epilogue stores overlap the other's main loop
-  static_assert(BNT == 256 || (BNT == 128 && WAVES == 4), "tile / waves");
+  // 256 x 256 tiles, 8 waves as 4 x 2 (wave 64 x 128): the one shape instantiated.  WAVES
+  // and BNT are the parameters of the retired 4-wave shapes (2 x 2 waves of 128 x 128;
+  // 256 x 128 tiles as 4 x 1), which the expressions below still cover; the parameter
+  // list stays so that the kernels keep their names
+  static_assert(WAVES == 8 && BNT == 256, "tile / waves");
   constexpr int WGM = (BNT == 128 || WAVES == 8) ? 4 : 2, WGN = WAVES / WGM, NTHR = 64 * WAVES;
   constexpr int WM = BM / WGM, WN = BN / WGN;
   constexpr int MT = WM / 32, NT = WN / 32;
@@ -305,164 +302,24 @@ __global__ __launch_bounds__(64 * WAVES) void gemm_x6p_kernel(GemmParams p) {
                                        addend, M, N, ldc, m0, n0);
 }
 
-
-// ---- 16x16x32 variant ("x6q") ---------------------------------------------------
-// Same operands and arithmetic as gemm_x6p_kernel, on v_mfma_f32_16x16x32_bf16:
-// at equal FLOPs the 16x16x32 stream holds a higher clock than the 32x32x16 one on
-// random data (tools/mfma_shape_bench.hip: 1.26x; MI355X_MICROARCH.md "DVFS
-// give-back" item 7).  Tile 256 x 128 x 32 (k), 8 waves as 4 x 2, each wave 64 x 64
-// as 4 x 4 blocks of 16 x 16; two 72-KB stages (one k-tile in flight measured as
-// fast as two for gemm_x6p).  A image [plane][k-tile of 32][Mp][32]; LDS: A rows of
-// 64 B with the 16-B slots XORed by (m >> 2) & 3, B rows of 256 B with the 16-B
-// units XORed by 2 (r & 3) + 8 ((r >> 3) & 1): both conflict-free for the
-// ds_read_b128 / ds_read_b64_tr_b16 fragments of the 16x16x32 shape.
-constexpr int X6Q_BM = 256, X6Q_BN = 128, X6Q_BK = 32;
-
-template <int EPI>
-__global__ __launch_bounds__(512) void gemm_x6q_kernel(GemmParams p) {
-  constexpr int BM = X6Q_BM, BN = X6Q_BN, BK = X6Q_BK;
-  constexpr int WGM = 4, WGN = 2;
-  constexpr int WM = BM / WGM, WN = BN / WGN;  // 64 x 64
-  constexpr int MT = WM / 16, NT = WN / 16;
-  constexpr int A_PLANE = BM * BK, B_PLANE = BK * BN;
-  constexpr int STAGE = 3 * (A_PLANE + B_PLANE);  // 72 KB
-  constexpr int NSTAGE = 2;
-  constexpr int RING_BYTES = NSTAGE * STAGE * 2;
-  constexpr int EPI_BYTES = 16 * WGM * (BN + 8) * 4;
-  constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
-  constexpr bool HAS_BIAS = (EPI & EPI_BIAS) != 0;
-  static_assert(STAGE * 2 == 72 * 1024, "stage = 48 A + 24 B pieces of 1 KB");
-  __shared__ __attribute__((aligned(16))) char lds_raw[LDS_BYTES + (HAS_BIAS ? BM * 4 : 0)];
-  unsigned short* const ring = reinterpret_cast<unsigned short*>(lds_raw);
-  float* const bias_s = reinterpret_cast<float*>(lds_raw + LDS_BYTES);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm = wave / WGN, wn = wave % WGN;
-  const int lin = xcd_remap(blockIdx.x, gridDim.x);
-  const int tm = lin % p.tiles_m, tn = lin / p.tiles_m;
-  const int z = blockIdx.z;
-  const unsigned short* Ax = p.Ax + z * p.sAx;
-  const unsigned short* Bx = p.Bx + z * p.sB;
-  float* C = p.C + z * p.sC;
-  const float* bias = p.bias ? p.bias + z * p.sBias : nullptr;
-  const float* addend = p.addend ? p.addend + z * p.sD : nullptr;
-  const int M = p.M, N = p.N, K = p.K, ldb = p.ldb, ldc = p.ldc;
-  const int Mp = p.ldax;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = (K + BK - 1) / BK;
-  if constexpr (HAS_BIAS) {
-    for (int r = tid; r < BM; r += 512) bias_s[r] = bias[min(m0 + r, M - 1)];
-  }
-  // LDS-DMA pieces c = wave + 8 q (q < 9): c < 48 -> A (plane c / 16, rows 16 (c % 16)),
-  // else B (plane (c - 48) / 8, k rows 4 ((c - 48) % 8))
-  const unsigned short* src[9];
-  int dst[9], brow[9];
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    const int c = wave + 8 * q;
-    if (c < 48) {
-      const int pl = c >> 4, rb = c & 15;
-      const int m = 16 * rb + (lane >> 2);
-      const int g = (lane & 3) ^ ((m >> 2) & 3);
-      src[q] = Ax + (int64_t)pl * p.sAxp + (int64_t)(m0 + m) * BK + 8 * g;
-      dst[q] = pl * A_PLANE + rb * 16 * BK;
-      brow[q] = -1;
-    } else {
-      const int cb = c - 48;
-      const int pl = cb >> 3, rq = cb & 7;
-      const int row = 4 * rq + (lane >> 4);
-      const int gu = (lane & 15) ^ (2 * (row & 3) + 8 * ((row >> 3) & 1));
-      src[q] = Bx + (int64_t)pl * p.sBxp + min(n0 + 8 * gu, ldb - 8);
-      dst[q] = 3 * A_PLANE + pl * B_PLANE + rq * 4 * BN;
-      brow[q] = row;
-    }
-  }
-  const int64_t a_kstride = (int64_t)Mp * BK;
-  const uint32_t ring_lds = lds_addr(ring);
-  auto issue = [&](int kt, int st) {
-    const uint32_t base = ring_lds + (uint32_t)(st * STAGE * 2);
-#pragma unroll
-    for (int q = 0; q < 9; ++q) {
-      const unsigned short* gp = brow[q] < 0
-                                     ? src[q] + kt * a_kstride
-                                     : src[q] + (int64_t)min(kt * BK + brow[q], K - 1) * ldb;
-      glds16(gp, base + (uint32_t)(dst[q] * 2));
-    }
-  };
-
-  floatx4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-  int a_off[MT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) {
-    const int row = wm * WM + i * 16 + (lane & 15);
-    a_off[i] = row * BK + 8 * ((lane >> 4) ^ ((row >> 2) & 3));
-  }
-  const int li = lane & 15, G = lane >> 4;
-  const int r1 = 8 * G + (li >> 2);  // k row of the first tr read (second: + 4)
-  const int fr = 2 * (r1 & 3) + 8 * ((r1 >> 3) & 1);
-  int b_off[NT];
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int c = wn * WN + j * 16 + 4 * (li & 3);
-    b_off[j] = 3 * A_PLANE + r1 * BN + (((c >> 3) ^ fr) << 3) + (c & 7);
-  }
-  auto mfma_tile = [&](int st) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const unsigned short* base = ring + st * STAGE;
-    bf16x8 a[MT][3];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-        a[i][pl] = *reinterpret_cast<const bf16x8*>(base + pl * A_PLANE + a_off[i]);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      bf16x8 b[3];
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-        const unsigned short* qq = base + pl * B_PLANE + b_off[j];
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)qq));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(qq + 4 * BN)));
-        const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-        b[pl] = __builtin_bit_cast(bf16x8, v);
-      }
-#pragma unroll
-      for (int i = 0; i < MT; ++i) SplitEng<3>::mma(a[i], b, acc[i][j]);
-    }
-  };
-
-  if constexpr (HAS_BIAS) __syncthreads();
-  issue(0, 0);
-  int st = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my DMA of k-tile kt landed
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // everyone's; the other stage is free
-    if (kt + 1 < nk) issue(kt + 1, st ^ 1);
-    __builtin_amdgcn_s_setprio(1);
-    mfma_tile(st);
-    __builtin_amdgcn_s_setprio(0);
-    st ^= 1;
-  }
-  __syncthreads();
-  gemm_epilogue<BM, BN, EPI, WGM, WGN, MT, NT, 16, floatx4>(
-      p, acc, reinterpret_cast<float*>(lds_raw), bias_s, C, addend, M, N, ldc, m0, n0);
-}
+// Nothing launches the three-stage ring any more, but it stays instantiated: it shares
+// gemm_epilogue<256, 256, EPI, 4, 2> with the launched two-stage kernel, and without it
+// hipcc schedules and allocates that kernel's epilogue differently (found by comparing
+// the assembly of each kernel; the 4-wave shapes, which share no epilogue, have no such
+// effect).  Kept so that the launched kernels stay the measured ones, byte for byte.
+template __global__ void gemm_x6p_kernel<0, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_RELU, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_RELU | EPI_PLANES, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_PLANES, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_BIAS, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_BIAS | EPI_ADD, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_ADD, 3>(GemmParams);
+template __global__ void gemm_x6p_kernel<EPI_BIAS | EPI_GELU | EPI_PLANES, 3>(GemmParams);
 
 // ---- host ---------------------------------------------------------------------
 
 size_t gemm_x6p_workspace(int M, int K, int batch_a) {
-  // k padded to 32: covers the 16-deep (x6p) and 32-deep (x6q) A images
+  // k padded to 32: two of the 16-deep k-tiles of the A image
   const int64_t Mp = round_up(M, X6P_BM), Kp = round_up(K, 32);
   return (size_t)round_up(3 * Mp * Kp * 2 * (int64_t)batch_a, 256);
 }
@@ -499,43 +356,12 @@ int launch_split_planes(const float* x, unsigned short* xp, int rows, int cols, 
   return launch_check("split_planes");
 }
 
-// MFMA shape of the plane GEMM: 32x32x16 (x6p) unless MSFNO_X6P_MFMA=16 (x6q,
-// measured 2 % slower on the fc2 shape); ring depth MSFNO_X6P_STAGES=2|3 (x6p; 2
-// k-tiles measured 1-3 % faster than 3 on fc1/fc2)
-static bool use_x6q() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_X6P_MFMA");
-    return e && std::string(e) == "16";
-  }();
-  return on;
-}
-
-// workgroup of the plane GEMM: 8 waves (default) or 4 (MSFNO_X6P_WAVES=4)
-static int x6p_waves() {
-  static const int w = [] {
-    const char* e = getenv("MSFNO_X6P_WAVES");
-    if (e && std::string(e) == "4x128") return 128;  // 256 x 128 tiles, 4 waves
-    return (e && e[0] == '4') ? 4 : 8;
-  }();
-  return w;
-}
-
+// two ring stages, 8 waves, 256 x 256 tiles: the one shape launched (DESIGN.md §9b,
+// "Retired in round 8", has the measurements of the three-stage ring, the 4-wave
+// workgroups and the 16x16x32 kernel)
 template <int EPI>
-static void launch_x6p_e(const GemmParams& p, dim3 grid, hipStream_t s, bool q) {
-  static const int stages = [] {
-    const char* e = getenv("MSFNO_X6P_STAGES");
-    return (e && e[0] == '3') ? 3 : 2;
-  }();
-  if (q)
-    hipLaunchKernelGGL((gemm_x6q_kernel<EPI>), grid, dim3(512), 0, s, p);
-  else if (stages == 2 && x6p_waves() == 4)
-    hipLaunchKernelGGL((gemm_x6p_kernel<EPI, 2, 4>), grid, dim3(256), 0, s, p);
-  else if (stages == 2 && x6p_waves() == 128)
-    hipLaunchKernelGGL((gemm_x6p_kernel<EPI, 2, 4, 128>), grid, dim3(256), 0, s, p);
-  else if (stages == 2)
-    hipLaunchKernelGGL((gemm_x6p_kernel<EPI, 2>), grid, dim3(512), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm_x6p_kernel<EPI, 3>), grid, dim3(512), 0, s, p);
+static void launch_x6p_e(const GemmParams& p, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_x6p_kernel<EPI, 2>), grid, dim3(512), 0, s, p);
 }
 
 int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, int ldc,
@@ -543,9 +369,7 @@ int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, in
              size_t ws_bytes, hipStream_t s) {
   if (M <= 0 || N <= 0 || batch <= 0) return MSFNO_OK;
   const int abatch = sA == 0 ? 1 : batch;
-  // the pre-split images of launch_spec_weights_x6p are 16-deep: x6p kernel for them
-  const bool q = use_x6q() && !epi.a_planes;
-  const int TKd = q ? X6Q_BK : X6P_BK;
+  constexpr int TKd = X6P_BK;
   const size_t need = (size_t)round_up(3 * round_up(M, X6P_BM) * round_up(K, TKd) * 2 * (int64_t)abatch, 256);
   MSFNO_REQUIRE(epi.a_planes || (ws && ws_bytes >= need), MSFNO_EINVAL,
                 "gemm_x6p: workspace too small");
@@ -563,12 +387,8 @@ int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, in
   } else {
     const int64_t pairs = (int64_t)Mp * KT * TKd / 2;
     const int blocks = (int)std::min<int64_t>(cdiv(pairs, 256), 1024);
-    if (q)
-      hipLaunchKernelGGL(split_a_tiles_kernel<X6Q_BK>, dim3(blocks, abatch), dim3(256), 0, s, A,
-                         Ax, M, K, lda, sA, Mp, KT);
-    else
-      hipLaunchKernelGGL(split_a_tiles_kernel<X6P_BK>, dim3(blocks, abatch), dim3(256), 0, s, A,
-                         Ax, M, K, lda, sA, Mp, KT);
+    hipLaunchKernelGGL(split_a_tiles_kernel<X6P_BK>, dim3(blocks, abatch), dim3(256), 0, s, A, Ax,
+                       M, K, lda, sA, Mp, KT);
     MSFNO_TRY(launch_check("split_a_tiles"));
   }
   GemmParams p{};
@@ -590,20 +410,20 @@ int gemm_x6p(const float* A, float* C, int M, int N, int K, int lda, int ldb, in
                       (reinterpret_cast<uintptr_t>(p.Cx) & 7) == 0,
                   MSFNO_EINVAL, "gemm_x6p: C planes need ld, strides % 4 == 0 and 8-B alignment");
   p.tiles_m = Mp / X6P_BM;
-  p.tiles_n = (int)cdiv(N, q ? X6Q_BN : (x6p_waves() == 128 ? 128 : X6P_BN));
+  p.tiles_n = (int)cdiv(N, X6P_BN);
   const dim3 grid(p.tiles_m * p.tiles_n, 1, batch);
   const int code = (p.bias ? EPI_BIAS : 0) | (p.addend ? EPI_ADD : 0) | (p.act == 1 ? EPI_GELU : 0) |
                    (p.relu_period ? EPI_RELU : 0) | (p.Cx ? EPI_PLANES : 0);
   switch (code) {
-    case 0: launch_x6p_e<0>(p, grid, s, q); break;
-    case EPI_RELU: launch_x6p_e<EPI_RELU>(p, grid, s, q); break;
-    case EPI_RELU | EPI_PLANES: launch_x6p_e<EPI_RELU | EPI_PLANES>(p, grid, s, q); break;
-    case EPI_PLANES: launch_x6p_e<EPI_PLANES>(p, grid, s, q); break;
-    case EPI_BIAS: launch_x6p_e<EPI_BIAS>(p, grid, s, q); break;
-    case EPI_BIAS | EPI_ADD: launch_x6p_e<EPI_BIAS | EPI_ADD>(p, grid, s, q); break;
-    case EPI_ADD: launch_x6p_e<EPI_ADD>(p, grid, s, q); break;
+    case 0: launch_x6p_e<0>(p, grid, s); break;
+    case EPI_RELU: launch_x6p_e<EPI_RELU>(p, grid, s); break;
+    case EPI_RELU | EPI_PLANES: launch_x6p_e<EPI_RELU | EPI_PLANES>(p, grid, s); break;
+    case EPI_PLANES: launch_x6p_e<EPI_PLANES>(p, grid, s); break;
+    case EPI_BIAS: launch_x6p_e<EPI_BIAS>(p, grid, s); break;
+    case EPI_BIAS | EPI_ADD: launch_x6p_e<EPI_BIAS | EPI_ADD>(p, grid, s); break;
+    case EPI_ADD: launch_x6p_e<EPI_ADD>(p, grid, s); break;
     case EPI_BIAS | EPI_GELU | EPI_PLANES:
-      launch_x6p_e<EPI_BIAS | EPI_GELU | EPI_PLANES>(p, grid, s, q); break;
+      launch_x6p_e<EPI_BIAS | EPI_GELU | EPI_PLANES>(p, grid, s); break;
     default:
       set_error("gemm_x6p: unsupported epilogue combination");
       return MSFNO_EUNSUPPORTED;

@@ -24,7 +24,6 @@
 // to 32, zero padded), so its staging is plain 16-B copies.
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "dma.h"
@@ -634,10 +633,7 @@ int legendre_x3f(const unsigned short* Ap, const float* isr,
   p.descs = descs; p.tile_desc = tile_desc;
   p.segA_w = segA_w; p.segA_stride = segA_stride;
   // MSFNO_X3F_NS=2: two LDS stages (49 KB, three workgroups per CU) instead of three
-  static const int ns = [] {
-    const char* e = getenv("MSFNO_X3F_NS");
-    return (e && e[0] == '2') ? 2 : 3;
-  }();
+  static const int ns = sw_char("MSFNO_X3F_NS") == '2' ? 2 : 3;
   if (ns == 2)
     hipLaunchKernelGGL(legendre_x3f_kernel<2>, dim3(tiles), dim3(256), 0, s, p);
   else

@@ -150,8 +150,10 @@ __device__ __forceinline__ const unsigned short* mf_slice_src(const MlpFusedPara
 template <int SCHED, int STAMP, int DBG = 0, int MF_AHEAD = 2, int XS = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void mlp_fused_kernel(MlpFusedParams p) {
-  // STAMP, DBG, XS: template parameters of retired diagnostic / A/B builds (a phase clock,
-  // timing builds with wrong results, cross-step prefetch); only <.., 0, 0, .., 0> is built
+  // SCHED, STAMP, DBG, MF_AHEAD, XS: template parameters of retired diagnostic / A/B builds
+  // (the compiler's own schedule, a phase clock, timing builds with wrong results, read-ahead
+  // depths 1 and 3, cross-step prefetch); only <1, 0, 0, 2, 0> is built
+  static_assert(SCHED == 1 && MF_AHEAD == 2, "only the scheduled two-ahead form is instantiated");
   // LDS: ring slots [0, 96K); x1 staging [24K, 152K) at the tile start (only slot 0
   // is live then); two 16-KB residual chunks [96K, 128K) during the steps; vectors at
   // the top
@@ -281,7 +283,6 @@ void mlp_fused_kernel(MlpFusedParams p) {
   // vector issue for 8 of its 32 cycles; MI355X_MICROARCH.md) instead of running
   // ahead of them as one serial stretch.
   auto kstep_schedule = [](bool reads) {
-    if constexpr (SCHED == 0) return;
     if (reads) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);  // DS read
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -613,10 +614,7 @@ void mlp_fused_kernel(MlpFusedParams p) {
 }
 
 bool mlp_fused_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_MLP_FUSED");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_MLP_FUSED");
   return on;
 }
 
@@ -657,25 +655,8 @@ int launch_mlp_fused(const float* x1, const float* scale, const float* shift, co
   p.tiles_per_field = (int)cdiv(P, MF_PX);
   const int64_t tiles = (int64_t)B * p.tiles_per_field;
   MSFNO_REQUIRE(tiles < (1LL << 31), MSFNO_EINVAL, "mlp_fused: grid too large");
-  // MSFNO_MF_SCHED=0: no explicit MFMA / VALU interleave (the compiler's schedule), for A/B
-  static const int sched = [] {
-    const char* e = getenv("MSFNO_MF_SCHED");
-    return e ? atoi(e) : 1;
-  }();
-  // MSFNO_MF_AHEAD=1|3: A-fragment read-ahead depth (default 2), for A/B
-  static const int ahead = [] {
-    const char* e = getenv("MSFNO_MF_AHEAD");
-    return e ? atoi(e) : 2;
-  }();
-  const dim3 grid((unsigned)tiles), blk(256);
-  if (!sched)
-    hipLaunchKernelGGL((mlp_fused_kernel<0, 0, 0, 2>), grid, blk, 0, s, p);
-  else if (ahead == 1)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 1>), grid, blk, 0, s, p);
-  else if (ahead == 3)
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 3>), grid, blk, 0, s, p);
-  else
-    hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 2>), grid, blk, 0, s, p);
+  // explicit MFMA / VALU interleave, A fragments read two steps ahead
+  hipLaunchKernelGGL((mlp_fused_kernel<1, 0, 0, 2>), dim3((unsigned)tiles), dim3(256), 0, s, p);
   return launch_check("mlp_fused");
 }
 

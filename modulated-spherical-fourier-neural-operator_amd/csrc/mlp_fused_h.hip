@@ -44,7 +44,6 @@
 #include "kernels.h"
 
 #include <cstdio>
-#include <string>
 #include <vector>
 #include <type_traits>
 
@@ -1014,10 +1013,7 @@ size_t skip_h_workspace(int B) {
 
 // MSFNO_SKIP_H=0 keeps gemm_x3 for the inner skip
 bool skip_h_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_SKIP_H");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_SKIP_H");
   return on;
 }
 
@@ -1039,16 +1035,8 @@ int launch_skip_h(const float* W, const float* xs, const float* x, float* out, c
   // the persistent pipelined kernel (MSFNO_SKIP_P=0: one tile per workgroup, read on
   // every call so one process can run both); its x pieces and output stores move 4
   // pixels per lane (P % 4 == 0)
-  const char* pe = getenv("MSFNO_SKIP_P");
-  const bool persist = !(pe && pe[0] == '0');
+  const bool persist = sw_on("MSFNO_SKIP_P");
   if (persist && P % 4 == 0) {
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-        n = 256;
-      return n;
-    }();
     SkipHPParams q{};
     q.x = x; q.xs = xs; q.out = out; q.img = img; q.inv_rs = inv_rs; q.bias = bias; q.P = P;
     q.tiles_per_field = (int)cdiv(P, SP_PX);
@@ -1063,9 +1051,9 @@ int launch_skip_h(const float* W, const float* xs, const float* x, float* out, c
     // against 163.6 / 164.3 / 162.8 for 2 per CU, 158.7 / 156.1 / 158.9 for 0.1875 and
     // 164.4 / 162.6 / 163.9 for 0.3125, three interleaved rounds (profiles/r06_f).
     // MSFNO_SKIP_GRID overrides both.
-    const char* ge = getenv("MSFNO_SKIP_GRID");
+    const char* ge = sw_raw("MSFNO_SKIP_GRID");  // (read on every call)
     const double per_cu = ge ? atof(ge) : (side ? 0.25 : 2.0);
-    const int64_t want = std::max<int64_t>(1, (int64_t)(per_cu * cus + 0.5));
+    const int64_t want = std::max<int64_t>(1, (int64_t)(per_cu * device_cus() + 0.5));
     const int grid = (int)std::min<int64_t>(t, want);
     hipLaunchKernelGGL(skip_hp_kernel, dim3((unsigned)grid), dim3(64 * SP_W), 0, s, q);
     return launch_check("skip_hp");
@@ -1077,10 +1065,7 @@ int launch_skip_h(const float* W, const float* xs, const float* x, float* out, c
 // the x3h engine is the default (measured as accurate as fp32 against fp64, more so
 // than x6: tests/test_gpu_x3h.py); MSFNO_ENGINE=x6 selects the six-MFMA bf16 engine
 bool mlp_fused_h_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_ENGINE");
-    return !(e && std::string(e) == "x6");
-  }();
+  static const bool on = !sw_eq("MSFNO_ENGINE", "x6");
   return on;
 }
 
@@ -1127,7 +1112,7 @@ int launch_mlp_fused_h(const float* x1, const float* scale, const float* shift,
   MSFNO_REQUIRE(tiles < (1LL << 31), MSFNO_EINVAL, "mlp_fused_h: grid too large");
   // MSFNO_MH_TRACE=<file> (diagnostic): each launch's per-workgroup CU ids and phase
   // timestamps are appended to <file> (synchronous; tools/mh_trace.py reads it)
-  const char* te = getenv("MSFNO_MH_TRACE");
+  const char* te = sw_raw("MSFNO_MH_TRACE");  // (read on every call)
   if (te && te[0]) {
     uint64_t* tb = nullptr;
     MSFNO_CHECK_HIP(hipMalloc(&tb, (size_t)tiles * 5 * 8));
@@ -1151,14 +1136,8 @@ int launch_mlp_fused_h(const float* x1, const float* scale, const float* shift,
   // MSFNO_MH_BUF=1: raw-buffer addressing of x1 / residual / output (a field's plane below
   // 2 GB).  Not the default: as fast (1.96 ms) but 3.98 instead of 3.36 GB of HBM traffic
   // per launch (profiles/r06_v vs r06_j pmc_traffic.json)
-  static const bool buf_env = [] {
-    const char* e = getenv("MSFNO_MH_BUF");
-    return e && e[0] == '1';
-  }();
-  static const bool ilv_env = [] {
-    const char* e = getenv("MSFNO_MH_ILV");
-    return !(e && e[0] == '0');
-  }();
+  static const bool buf_env = sw_is1("MSFNO_MH_BUF");
+  static const bool ilv_env = sw_on("MSFNO_MH_ILV");
   const bool buf = buf_env && (int64_t)MH_C * P * 4 < (1LL << 31);
   if (buf && ilv_env)
     hipLaunchKernelGGL((mlp_fused_h_kernel<2, false, true, true>), dim3((unsigned)tiles), dim3(64 * MH_WAVES), 0, s, p);

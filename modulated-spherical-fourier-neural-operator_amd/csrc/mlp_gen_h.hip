@@ -36,7 +36,6 @@
 
 #include <algorithm>
 #include <mutex>
-#include <string>
 #include <type_traits>
 #include <unordered_map>
 #include <utility>
@@ -964,10 +963,7 @@ bool mg_shape(int Ct, int Cout, int* ks, int* ot) {
 
 // MSFNO_MLP_GEN_H=0 keeps the two-GEMM x6 path for the standalone MLP
 static bool mlp_gen_h_env() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_MLP_GEN_H");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_MLP_GEN_H");
   return on;
 }
 
@@ -1001,10 +997,7 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
   // the persistent pipelined kernel (the encoder shape; MSFNO_MG_P=0 keeps one tile per
   // workgroup).  Its pieces and stores move 4 pixels per lane (P % 4 == 0) with 32-bit
   // byte offsets into a field
-  static const bool persist_env = [] {
-    const char* e = getenv("MSFNO_MG_P");
-    return !(e && e[0] == '0');
-  }();
+  static const bool persist_env = sw_on("MSFNO_MG_P");
   const bool persist = persist_env && KS == 3 && OT == 16 && HB == GP_HB && !xa && !x2 &&
                        P % 4 == 0 && P >= 4 && (int64_t)Cin * P * 4 < (1LL << 32) &&
                        (int64_t)Cout * P * 4 < (1LL << 31);
@@ -1050,18 +1043,11 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
   p.Cin = Cin; p.Cin2 = Cin2; p.Cout = Cout; p.H = H;
   p.nslice = (int)(tiles / MG_SLICE);
   if (persist) {
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-        n = 256;
-      return n;
-    }();
     p.tiles_per_field = (int)cdiv(P, GP_PX);
     const int64_t t = (int64_t)B * p.tiles_per_field;
     MSFNO_REQUIRE(t < (1LL << 31), MSFNO_EINVAL, "mlp_gen_hp: grid too large");
     p.tiles = (int)t;
-    const int grid = (int)std::min<int64_t>(t, cus);  // one workgroup fills a CU
+    const int grid = (int)std::min<int64_t>(t, device_cus());  // one workgroup fills a CU
     // ring depth 4 (5 and 6 measured equal with the x pieces in the ring slots,
     // profiles/r06_l; with the x buffer only 4 fits)
     const dim3 gd((unsigned)grid);
@@ -1072,10 +1058,7 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
     // without the GELU 0.16 ms less per net step, without the addend, x or store streams
     // 0.01-0.05 ms less each; the fc1 steps' VALU forced between their MFMAs
     // (sched_group_barrier, 2 / 4 / 6 per MFMA) changed nothing (summary_s.txt)
-    static const int pg = [] {
-      const char* e = getenv("MSFNO_MG_PG");
-      return e && e[0] == '1' ? 1 : 2;
-    }();
+    static const int pg = sw_is1("MSFNO_MG_PG") ? 1 : 2;
     const dim3 bd2(64 * (8 / pg));
     if (pg == 1) {
       if (addend) hipLaunchKernelGGL((mlp_gen_hp_kernel<3, 16, true, 4, 1>), gd, bd2, 0, s, p);
@@ -1093,13 +1076,9 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
   // 2.35 / 2.33 / 2.34 ms per 12-block step, net 124.5 / 124.0 / 123.9 -> 125.6 / 125.7 /
   // 125.7 steps/s (three interleaved pairs, profiles/r06_h); MSFNO_MG_EARLY=0 restores
   // the late form
-  const char* ee = getenv("MSFNO_MG_EARLY");
-  const bool early = !(ee && ee[0] == '0');
+  const bool early = sw_on("MSFNO_MG_EARLY");  // (read on every call)
   // raw-buffer addressing (MSFNO_MG_BUF=0: 64-bit addresses, A/B)
-  static const bool buf_env = [] {
-    const char* e = getenv("MSFNO_MG_BUF");
-    return !(e && e[0] == '0');
-  }();
+  static const bool buf_env = sw_on("MSFNO_MG_BUF");
   const int64_t lim = 1LL << 31;
   const bool buf = buf_env && (x2 == nullptr || Cin % 32 == 0) && (int64_t)Cin * P * 4 < lim &&
                    (int64_t)Cin2 * P * 4 < lim && (int64_t)Cout * P * 4 < lim;

@@ -5,9 +5,6 @@
 //   * weight preparation (complex block expansion, norm/FiLM folding into fc1),
 //   * the linear filter's per-mode complex contraction (HBM weight stream),
 //   * S-layout conversions (reference dense (l,m) / torch.tril_indices order).
-#include <cstring>
-#include <string>
-
 #include "dma.h"
 #include "kernels.h"
 #include "split_engine.h"
@@ -20,9 +17,6 @@ constexpr float kTwoPi = 6.28318530717958647692f;
 // transposes
 // ---------------------------------------------------------------------------
 constexpr int TK = 64, TMM = 32;
-// symmetric transposes, tiles (latitudes x m) measured at 721 x 1440 among 64x32,
-// 32x64, 64x64 and 32x32: forward 64 x 32 (0.31 ms), inverse 32 x 64 (0.27 vs 0.30 ms)
-constexpr int TK_FWD = 64, TM_FWD = 32, TK_INV = 32, TM_INV = 64;
 
 __global__ __launch_bounds__(256) void transpose_fwd_kernel(const float2* __restrict__ Xn,
                                                             float* __restrict__ Xt, int B, int C,
@@ -122,137 +116,11 @@ int launch_transpose_inv(const float* Yt, float2* Yn, int B, int C, int nlat, in
 // an odd grid once) into slab columns [0, Ke) and Xa_k = X_k - X_{n-1-k} (k < Ko)
 // into [ldke, ldke + Ko); the inverse one unfolds Y_k = E_k + O_k,
 // Y_{n-1-k} = E_k - O_k from the even/odd Legendre outputs.
-template <int TKx, int TMx>
-__global__ __launch_bounds__(256) void transpose_fwd_sym_kernel(
-    const float2* __restrict__ Xn, float* __restrict__ Xt, int B, int C, LatGeom g, int mmax,
-    const float* __restrict__ nscale, const float* __restrict__ nshift,
-    const int* __restrict__ slab, int kpad) {
-  __shared__ float2 tn[TMx][TKx + 1], ts[TMx][TKx + 1];
-  const int k0 = blockIdx.x * TKx, m0 = blockIdx.y * TMx;
-  const int bc = blockIdx.z;
-  const int b = bc / C, c = bc - b * C;
-  const float2* src = Xn + (int64_t)bc * g.nlat * mmax;
-  for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-    const int kk = i / TMx, mm = i - kk * TMx;
-    const int k = k0 + kk, m = m0 + mm;
-    float2 vn = make_float2(0.f, 0.f), vs = vn;
-    if (k < g.Ke && m < mmax) {
-      vn = src[(int64_t)k * mmax + m];
-      if (k < g.nh) vs = src[(int64_t)(g.nlat - 1 - k) * mmax + m];
-    }
-    tn[mm][kk] = vn;
-    ts[mm][kk] = vs;
-  }
-  __syncthreads();
-  const float sc = nscale ? nscale[bc] : 1.f;
-  const float sh = nshift ? nshift[bc] * kTwoPi : 0.f;
-  const int64_t R = 2LL * B * C;
-  const int64_t rre = (int64_t)(b * 2 + 0) * C + c;
-  const int64_t rim = (int64_t)(b * 2 + 1) * C + c;
-  for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-    const int mm = i / TKx, kk = i - mm * TKx;
-    const int k = k0 + kk, m = m0 + mm;
-    if (m >= mmax) continue;
-    const int sl = slab ? slab[m] : m;
-    if (sl < 0) continue;
-    float* dst = Xt + (int64_t)sl * R * g.ldk;
-    if (k >= g.Ke) {  // band exchange pads (read by the GEMM): Xs [Ke, kpad), Xa [nh, kpad)
-      if (k < kpad) {
-        dst[rre * g.ldk + k] = 0.f;
-        dst[rim * g.ldk + k] = 0.f;
-        dst[rre * g.ldk + g.ldke + k] = 0.f;
-        dst[rim * g.ldk + g.ldke + k] = 0.f;
-      }
-      continue;
-    }
-    const float2 n = tn[mm][kk], q = ts[mm][kk];
-    const float shm = (m == 0) ? sh : 0.f;
-    const bool pair = k < g.nh;
-    // affine per row, then fold: s(N + S) + 2t  /  s(N - S)
-    dst[rre * g.ldk + k] = pair ? fmaf(sc, n.x + q.x, 2.f * shm) : fmaf(sc, n.x, shm);
-    dst[rim * g.ldk + k] = pair ? sc * (n.y + q.y) : sc * n.y;
-    if (pair) {
-      dst[rre * g.ldk + g.ldke + k] = sc * (n.x - q.x);
-      dst[rim * g.ldk + g.ldke + k] = sc * (n.y - q.y);
-    } else if (k < kpad) {
-      dst[rre * g.ldk + g.ldke + k] = 0.f;
-      dst[rim * g.ldk + g.ldke + k] = 0.f;
-    }
-  }
-}
-
-// Two-phase variants: ONE LDS tile, written twice (Xs then Xa forward, north then
-// south rows inverse) from values the threads hold in registers, so a 32 x 128 tile
-// fits in 33 KB: rows of 128 m (1 KB) on the spectrum side and whole 128-B lines of
-// 32 latitudes on the slab side (the one-phase 16 x 128 / 64 x 32 tiles fetch half
-// lines: PMC read bytes 2.0x / 1.5x the algorithmic ones)
-template <int TKx, int TMx>
-__global__ __launch_bounds__(256) void transpose_fwd_sym2_kernel(
-    const float2* __restrict__ Xn, float* __restrict__ Xt, int B, int C, LatGeom g, int mmax,
-    const float* __restrict__ nscale, const float* __restrict__ nshift,
-    const int* __restrict__ slab, int kpad) {
-  constexpr int PER = TKx * TMx / 256;
-  static_assert(PER * 256 == TKx * TMx, "tile");
-  __shared__ float2 tile[TMx][TKx + 1];
-  const int k0 = blockIdx.x * TKx, m0 = blockIdx.y * TMx;
-  const int bc = blockIdx.z;
-  const int b = bc / C, c = bc - b * C;
-  const float2* src = Xn + (int64_t)bc * g.nlat * mmax;
-  const float sc = nscale ? nscale[bc] : 1.f;
-  const float sh = nshift ? nshift[bc] * kTwoPi : 0.f;
-  float2 xs[PER], xa[PER];
-#pragma unroll
-  for (int q = 0; q < PER; ++q) {
-    const int i = threadIdx.x + 256 * q;
-    const int kk = i / TMx, mm = i - kk * TMx;
-    const int k = k0 + kk, m = m0 + mm;
-    float2 n = make_float2(0.f, 0.f), t = n;
-    if (k < g.Ke && m < mmax) {
-      n = src[(int64_t)k * mmax + m];
-      if (k < g.nh) t = src[(int64_t)(g.nlat - 1 - k) * mmax + m];
-    }
-    const bool pair = k < g.nh;
-    const float shm = (m == 0) ? sh : 0.f;
-    // affine per row, then fold: s(N + S) + 2t  /  s(N - S)
-    xs[q] = k >= g.Ke ? make_float2(0.f, 0.f)  // band pads
-            : pair ? make_float2(fmaf(sc, n.x + t.x, 2.f * shm), sc * (n.y + t.y))
-                   : make_float2(fmaf(sc, n.x, shm), sc * n.y);
-    xa[q] = pair ? make_float2(sc * (n.x - t.x), sc * (n.y - t.y)) : make_float2(0.f, 0.f);
-  }
-  const int64_t R = 2LL * B * C;
-  const int64_t rre = (int64_t)(b * 2 + 0) * C + c;
-  const int64_t rim = (int64_t)(b * 2 + 1) * C + c;
-  const int kend = max(g.Ke, kpad);
-#pragma unroll
-  for (int ph = 0; ph < 2; ++ph) {
-    if (ph) __syncthreads();
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = threadIdx.x + 256 * q;
-      const int kk = i / TMx, mm = i - kk * TMx;
-      tile[mm][kk] = ph ? xa[q] : xs[q];
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-      const int mm = i / TKx, kk = i - mm * TKx;
-      const int k = k0 + kk, m = m0 + mm;
-      if (k >= kend || m >= mmax) continue;
-      const int sl = slab ? slab[m] : m;
-      if (sl < 0) continue;
-      // real values for k < Ke (Xs) / k < nh (Xa); zeros on the pads up to kpad
-      if (k >= (ph ? (kpad > 0 ? kend : g.nh) : kend)) continue;
-      const float2 v = tile[mm][kk];
-      float* dst = Xt + (int64_t)sl * R * g.ldk + (ph ? g.ldke : 0) + k;
-      dst[rre * g.ldk] = v.x;
-      dst[rim * g.ldk] = v.y;
-    }
-  }
-}
-
-// Vector-store variant: the fold + affine in registers on the load side (8-B loads of
+//
+// Forward, vector stores: the fold + affine in registers on the load side (8-B loads of
 // the north and mirror rows), the four slab rows of one m (Xs re / im, Xa re / im)
 // as LDS rows of TKx floats, stored as 16-B vectors (a 64-lane instruction writes
-// four 256-B row segments; the scalar-store kernels above write one).  Whole float4
+// four 256-B row segments; a scalar store writes one).  Whole float4
 // units up to round4(end of the valid k range) are written, zeros past it (pads).
 template <int TKx, int TMx>
 __global__ __launch_bounds__(256) void transpose_fwd_sym4_kernel(
@@ -305,14 +173,13 @@ __global__ __launch_bounds__(256) void transpose_fwd_sym4_kernel(
   }
 }
 
-// Block order of the symmetric transposes (XR): the spectra rows (mmax float2 = 2888 B at
-// 721x1440) and the slab rows start off the 128-B line grid, so two neighbouring tiles
-// share the lines at their common edge; the hardware deals blocks round-robin over the
-// 8 XCDs, which puts neighbours in different L2s, and each fetches the shared line from
-// HBM (PMC: reads 1.5x the algorithmic bytes, profiles/r06_v).  XR = 1 / 2: a 1-D grid
-// whose ids tr_remap makes contiguous per XCD, decoded m-tile fastest (1) or
-// latitude-tile fastest (2: the hardware's own order, but with neighbours in one XCD).
-// XR = 0: the plain 3-D grid.
+// Block order of the symmetric transposes (XR = 2, the only one instantiated): the spectra
+// rows (mmax float2 = 2888 B at 721x1440) and the slab rows start off the 128-B line grid,
+// so two neighbouring tiles share the lines at their common edge; the hardware deals
+// blocks round-robin over the 8 XCDs, which puts neighbours in different L2s, and each
+// fetches the shared line from HBM (PMC: reads 1.5x the algorithmic bytes,
+// profiles/r06_v).  So: a 1-D grid whose ids tr_remap makes contiguous per XCD, decoded
+// latitude-tile fastest (the hardware's own order, but with neighbours in one XCD).
 __device__ __forceinline__ int tr_remap(int orig, int nwg) {  // = gemm_common.h xcd_remap
   const int xcd = orig & 7;
   const int q = nwg >> 3, r = nwg & 7;
@@ -321,32 +188,13 @@ __device__ __forceinline__ int tr_remap(int orig, int nwg) {  // = gemm_common.h
 
 template <int XR>
 __device__ __forceinline__ int3 tr_block(int nx, int ny) {
-  if constexpr (XR == 0) {
-    return make_int3((int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z);
-  } else if constexpr (XR == 1) {
-    const int lin = tr_remap((int)blockIdx.x, (int)gridDim.x);
-    const int y = lin % ny, r = lin / ny;
-    return make_int3(r % nx, y, r / nx);
-  } else {
-    const int lin = tr_remap((int)blockIdx.x, (int)gridDim.x);
-    const int x = lin % nx, r = lin / nx;
-    return make_int3(x, r % ny, r / ny);
-  }
+  static_assert(XR == 2, "only the per-XCD contiguous order is instantiated");
+  const int lin = tr_remap((int)blockIdx.x, (int)gridDim.x);
+  const int x = lin % nx, r = lin / nx;
+  return make_int3(x, r % ny, r / ny);
 }
 
-static dim3 tr_grid(int xr, int nx, int ny, int nz) {
-  return xr ? dim3((unsigned)(nx * ny * nz)) : dim3((unsigned)nx, (unsigned)ny, (unsigned)nz);
-}
-
-// MSFNO_TR_XCD = "<forward><inverse>" block orders (A/B; "00": the plain 3-D grids)
-static int tr_xcd(int which) {
-  static const std::string v = [] {
-    const char* e = getenv("MSFNO_TR_XCD");
-    return std::string(e && strlen(e) == 2 ? e : "22");
-  }();
-  const int d = v[which] - '0';
-  return d >= 0 && d <= 2 ? d : 2;
-}
+static dim3 tr_grid(int nx, int ny, int nz) { return dim3((unsigned)(nx * ny * nz)); }
 
 template <int TKx, int TMx>
 static void fwd_sym4h_launch(const float2* Xn, unsigned short* Xp, int B, int C, const LatGeom& g,
@@ -384,7 +232,7 @@ __global__ __launch_bounds__(256) void transpose_fwd_sym4h_kernel(
   const int64_t R = 2LL * B * C;
   if (blk.x == 0 && blk.y == 0 && threadIdx.x < 2)
     isr[(int64_t)(b * 2 + threadIdx.x) * C + c] = 1.f / sig;
-  // the tile's values: every load of a thread issued before the first is used (PRE; the
+  // the tile's values: every load of a thread issued before the first is used (PRE; a
   // rolled loop kept two 8-B loads per wave in flight), then folded into the LDS tile
   auto put = [&](int kk, int mm, float2 n, float2 t) {
     const int k = k0 + kk, m = m0 + mm;
@@ -406,26 +254,19 @@ __global__ __launch_bounds__(256) void transpose_fwd_sym4h_kernel(
       if (k < g.nh) t = src[(int64_t)(g.nlat - 1 - k) * mmax + m];
     }
   };
-  if constexpr (PRE) {
-    constexpr int PER = TKx * TMx / 256;
-    static_assert(PER * 256 == TKx * TMx, "tile");
-    float2 nv[PER], tv[PER];
+  static_assert(PRE, "only the preloading form is instantiated");
+  constexpr int PER = TKx * TMx / 256;
+  static_assert(PER * 256 == TKx * TMx, "tile");
+  float2 nv[PER], tv[PER];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = threadIdx.x + 256 * q;
-      fetch(i / TMx, i % TMx, nv[q], tv[q]);
-    }
+  for (int q = 0; q < PER; ++q) {
+    const int i = threadIdx.x + 256 * q;
+    fetch(i / TMx, i % TMx, nv[q], tv[q]);
+  }
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = threadIdx.x + 256 * q;
-      put(i / TMx, i % TMx, nv[q], tv[q]);
-    }
-  } else {
-    for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-      float2 n, t;
-      fetch(i / TMx, i % TMx, n, t);
-      put(i / TMx, i % TMx, n, t);
-    }
+  for (int q = 0; q < PER; ++q) {
+    const int i = threadIdx.x + 256 * q;
+    put(i / TMx, i % TMx, nv[q], tv[q]);
   }
   __syncthreads();
   // 8 k per thread: one 16-B store per plane (ldke, ldk are multiples of 8)
@@ -485,25 +326,19 @@ static void fwd_sym4h_launch(const float2* Xn, unsigned short* Xp, int B, int C,
                              int mmax, const float* nscale, const float* nshift,
                              const float* lsig, float* isr, const int* perm, int kext,
                              hipStream_t s) {
-  const int nx = cdiv(kext, TKx), ny = cdiv(mmax, TMx), xr = tr_xcd(0);
-  const dim3 grid = tr_grid(xr, nx, ny, B * C);
-  static const bool pre = [] {
-    const char* e = getenv("MSFNO_TR_FWD_PRE");
-    return !(e && e[0] == '0');
-  }();
-#define MSFNO_SYM4H(XR, PRE)                                                                     \
-  hipLaunchKernelGGL((transpose_fwd_sym4h_kernel<TKx, TMx, XR, PRE>), grid, dim3(256), 0, s, Xn, \
-                     Xp, B, C, g, mmax, nscale, nshift, lsig, isr, perm, nx, ny)
-  if (xr == 2 && pre) MSFNO_SYM4H(2, true);
-  else if (xr == 2) MSFNO_SYM4H(2, false);
-  else if (xr == 1) MSFNO_SYM4H(1, false);
-  else MSFNO_SYM4H(0, false);
-#undef MSFNO_SYM4H
+  const int nx = cdiv(kext, TKx), ny = cdiv(mmax, TMx);
+  hipLaunchKernelGGL((transpose_fwd_sym4h_kernel<TKx, TMx, 2, true>), tr_grid(nx, ny, B * C),
+                     dim3(256), 0, s, Xn, Xp, B, C, g, mmax, nscale, nshift, lsig, isr, perm, nx,
+                     ny);
 }
 
-// BF: the loads are branch-free (clamped addresses, the values selected afterwards), so a
-// thread's 64 loads are all in flight at once; with the range tests as branches the
-// compiler drained them per branch (33 vmcnt(0) waits, at most 4 loads in flight)
+// Inverse, two phases: ONE LDS tile, written twice (north then south rows) from values the
+// threads hold in registers, so a 32 x 128 tile fits in 33 KB: rows of 128 m (1 KB) on the
+// spectrum side and whole 128-B lines of 32 latitudes on the slab side.
+// BF (the only form instantiated): the loads are branch-free (clamped addresses, the
+// values selected afterwards), so a thread's 64 loads are all in flight at once; with the
+// range tests as branches the compiler drained them per branch (33 vmcnt(0) waits, at
+// most 4 loads in flight)
 template <int TKx, int TMx, int XR, bool BF>
 __global__ __launch_bounds__(256) void transpose_inv_sym2_kernel(const float* __restrict__ Yt,
                                                                  float2* __restrict__ Yn, int B,
@@ -521,63 +356,40 @@ __global__ __launch_bounds__(256) void transpose_inv_sym2_kernel(const float* __
   const int64_t R = 2LL * B * C;
   const int64_t rre = (int64_t)(b * 2 + 0) * C + c;
   const int64_t rim = (int64_t)(b * 2 + 1) * C + c;
+  static_assert(BF, "only the branch-free form is instantiated");
   float2 yn[PER], ys[PER];
-  if constexpr (BF) {
-    // the slab of every m first (one wait), then all 4 PER loads at clamped addresses;
-    // the empty asm uses each value unconditionally, so the compiler cannot sink a
-    // load into the branch of its range test
-    int slq[PER];
+  // the slab of every m first (one wait), then all 4 PER loads at clamped addresses;
+  // the empty asm uses each value unconditionally, so the compiler cannot sink a
+  // load into the branch of its range test
+  int slq[PER];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int m = m0 + (threadIdx.x + 256 * q) / TKx;
-      slq[q] = (m < mact) ? (slab ? slab[min(m, mact - 1)] : m) : -1;
-    }
-    float er[PER], ei[PER], orr[PER], oi[PER];
+  for (int q = 0; q < PER; ++q) {
+    const int m = m0 + (threadIdx.x + 256 * q) / TKx;
+    slq[q] = (m < mact) ? (slab ? slab[min(m, mact - 1)] : m) : -1;
+  }
+  float er[PER], ei[PER], orr[PER], oi[PER];
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = threadIdx.x + 256 * q;
-      const int k = k0 + (i % TKx);
-      const bool ok = k < g.Ke && slq[q] >= 0, pr = ok && k < g.nh;
-      const float* srcp = Yt + (int64_t)(ok ? slq[q] : 0) * R * g.ldk;
-      const int ke = ok ? k : 0, ko = g.ldke + (pr ? k : 0);
-      er[q] = srcp[rre * g.ldk + ke];
-      ei[q] = srcp[rim * g.ldk + ke];
-      orr[q] = srcp[rre * g.ldk + ko];
-      oi[q] = srcp[rim * g.ldk + ko];
-    }
+  for (int q = 0; q < PER; ++q) {
+    const int i = threadIdx.x + 256 * q;
+    const int k = k0 + (i % TKx);
+    const bool ok = k < g.Ke && slq[q] >= 0, pr = ok && k < g.nh;
+    const float* srcp = Yt + (int64_t)(ok ? slq[q] : 0) * R * g.ldk;
+    const int ke = ok ? k : 0, ko = g.ldke + (pr ? k : 0);
+    er[q] = srcp[rre * g.ldk + ke];
+    ei[q] = srcp[rim * g.ldk + ke];
+    orr[q] = srcp[rre * g.ldk + ko];
+    oi[q] = srcp[rim * g.ldk + ko];
+  }
 #pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      asm volatile("" : "+v"(er[q]), "+v"(ei[q]), "+v"(orr[q]), "+v"(oi[q]));
-      const int i = threadIdx.x + 256 * q;
-      const int k = k0 + (i % TKx);
-      const bool ok = k < g.Ke && slq[q] >= 0, pr = ok && k < g.nh;
-      const float2 e = ok ? make_float2(er[q], ei[q]) : make_float2(0.f, 0.f);
-      const float2 o = pr ? make_float2(orr[q], oi[q]) : make_float2(0.f, 0.f);
-      yn[q] = make_float2(e.x + o.x, e.y + o.y);
-      ys[q] = pr ? make_float2(e.x - o.x, e.y - o.y) : make_float2(0.f, 0.f);
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = threadIdx.x + 256 * q;
-      const int mm = i / TKx, kk = i - mm * TKx;
-      const int k = k0 + kk, m = m0 + mm;
-      float2 n = make_float2(0.f, 0.f), t = n;
-      const int sl = (m < mact) ? (slab ? slab[m] : m) : -1;
-      if (k < g.Ke && sl >= 0) {
-        const float* srcp = Yt + (int64_t)sl * R * g.ldk;
-        const float2 e = make_float2(srcp[rre * g.ldk + k], srcp[rim * g.ldk + k]);
-        if (k < g.nh) {
-          const float2 o = make_float2(srcp[rre * g.ldk + g.ldke + k], srcp[rim * g.ldk + g.ldke + k]);
-          n = make_float2(e.x + o.x, e.y + o.y);
-          t = make_float2(e.x - o.x, e.y - o.y);
-        } else {
-          n = e;
-        }
-      }
-      yn[q] = n;
-      ys[q] = t;
-    }
+  for (int q = 0; q < PER; ++q) {
+    asm volatile("" : "+v"(er[q]), "+v"(ei[q]), "+v"(orr[q]), "+v"(oi[q]));
+    const int i = threadIdx.x + 256 * q;
+    const int k = k0 + (i % TKx);
+    const bool ok = k < g.Ke && slq[q] >= 0, pr = ok && k < g.nh;
+    const float2 e = ok ? make_float2(er[q], ei[q]) : make_float2(0.f, 0.f);
+    const float2 o = pr ? make_float2(orr[q], oi[q]) : make_float2(0.f, 0.f);
+    yn[q] = make_float2(e.x + o.x, e.y + o.y);
+    ys[q] = pr ? make_float2(e.x - o.x, e.y - o.y) : make_float2(0.f, 0.f);
   }
   float2* dst = Yn + (int64_t)bc * g.nlat * mmax;
 #pragma unroll
@@ -599,59 +411,18 @@ __global__ __launch_bounds__(256) void transpose_inv_sym2_kernel(const float* __
   }
 }
 
-// tile shape (latitudes x m) of the symmetric transposes: MSFNO_TR_FWD / MSFNO_TR_INV =
-// "64x32" | "32x64" | "32x128" | "16x128" | "2p" | "v4" (A/B; defaults v4 forward: the
-// 64x32 tile with 16-B stores, 0.265 vs 0.280 ms for 64x32 in two interleaved in-block
-// runs (round 3); 2p inverse: 0.247-0.248 vs 0.255-0.258 ms for 16x128 in four interleaved in-block runs
-// at 721x1440, C = 256 (16x128: 0.257 vs 0.268 ms for 32x64); the 32x128 one-phase
-// tiles (67 KB of LDS) lose occupancy: 0.58 / 0.34 ms)
-static int tr_tile(const char* var, int dflt) {
-  const char* e = getenv(var);
-  if (!e) return dflt;
-  const std::string v(e);
-  return v == "64x32" ? 0 : v == "32x64" ? 1 : v == "32x128" ? 2 : v == "16x128" ? 3
-         : v == "2p" ? 4 : v == "v4" ? 5 : dflt;
-}
-
-template <int TKx, int TMx>
+// the fp32 slab (and the band pack): 64 x 32 tiles with 16-B stores
 static void fwd_sym_launch(const float2* Xn, float* Xt, int B, int C, const LatGeom& g, int mmax,
                            const float* nscale, const float* nshift, const int* perm, int kpad,
                            hipStream_t s) {
-  dim3 grid((unsigned)cdiv(std::max(g.Ke, kpad), TKx), (unsigned)cdiv(mmax, TMx),
-            (unsigned)(B * C));
-  hipLaunchKernelGGL((transpose_fwd_sym_kernel<TKx, TMx>), grid, dim3(256), 0, s, Xn, Xt, B, C,
-                     g, mmax, nscale, nshift, perm, kpad);
-}
-
-static void fwd_sym_dispatch(const float2* Xn, float* Xt, int B, int C, const LatGeom& g,
-                             int mmax, const float* nscale, const float* nshift, const int* perm,
-                             int kpad, hipStream_t s) {
-  static const int t = tr_tile("MSFNO_TR_FWD", 5);
-  switch (t) {
-    case 1: fwd_sym_launch<32, 64>(Xn, Xt, B, C, g, mmax, nscale, nshift, perm, kpad, s); break;
-    case 2: fwd_sym_launch<32, 128>(Xn, Xt, B, C, g, mmax, nscale, nshift, perm, kpad, s); break;
-    case 3: fwd_sym_launch<16, 128>(Xn, Xt, B, C, g, mmax, nscale, nshift, perm, kpad, s); break;
-    case 4: {
-      dim3 grid((unsigned)cdiv(std::max(g.Ke, kpad), 32), (unsigned)cdiv(mmax, 128),
-                (unsigned)(B * C));
-      hipLaunchKernelGGL((transpose_fwd_sym2_kernel<32, 128>), grid, dim3(256), 0, s, Xn, Xt, B,
-                         C, g, mmax, nscale, nshift, perm, kpad);
-      break;
-    }
-    case 5: {
-      dim3 grid((unsigned)cdiv(std::max(g.Ke, kpad), 64), (unsigned)cdiv(mmax, 32),
-                (unsigned)(B * C));
-      hipLaunchKernelGGL((transpose_fwd_sym4_kernel<64, 32>), grid, dim3(256), 0, s, Xn, Xt, B,
-                         C, g, mmax, nscale, nshift, perm, kpad);
-      break;
-    }
-    default: fwd_sym_launch<TK_FWD, TM_FWD>(Xn, Xt, B, C, g, mmax, nscale, nshift, perm, kpad, s);
-  }
+  dim3 grid((unsigned)cdiv(std::max(g.Ke, kpad), 64), (unsigned)cdiv(mmax, 32), (unsigned)(B * C));
+  hipLaunchKernelGGL((transpose_fwd_sym4_kernel<64, 32>), grid, dim3(256), 0, s, Xn, Xt, B, C, g,
+                     mmax, nscale, nshift, perm, kpad);
 }
 
 int launch_transpose_fwd_sym(const float2* Xn, float* Xt, int B, int C, const LatGeom& g, int mmax,
                              const float* nscale, const float* nshift, hipStream_t s) {
-  fwd_sym_dispatch(Xn, Xt, B, C, g, mmax, nscale, nshift, nullptr, 0, s);
+  fwd_sym_launch(Xn, Xt, B, C, g, mmax, nscale, nshift, nullptr, 0, s);
   return launch_check("transpose_fwd_sym");
 }
 
@@ -665,98 +436,21 @@ int launch_band_pack(const float2* Xn, float* send, int B, int C, const LatGeom&
   if (!g.sym)
     return launch_transpose_fwd(Xn, send, B, C, g.nlat, mmax, g.ldk, nscale, nshift, s, perm,
                                 2 * W);
-  fwd_sym_dispatch(Xn, send, B, C, g, mmax, nscale, nshift, perm, W, s);
+  fwd_sym_launch(Xn, send, B, C, g, mmax, nscale, nshift, perm, W, s);
   return launch_check("band_pack");
 }
 
-
-template <int TKx, int TMx>
-__global__ __launch_bounds__(256) void transpose_inv_sym_kernel(const float* __restrict__ Yt,
-                                                                float2* __restrict__ Yn, int B,
-                                                                int C, LatGeom g, int mmax,
-                                                                int mact,
-                                                                const int* __restrict__ slab) {
-  __shared__ float2 tn[TMx][TKx + 1], ts[TMx][TKx + 1];
-  const int k0 = blockIdx.x * TKx, m0 = blockIdx.y * TMx;
-  const int bc = blockIdx.z;
-  const int b = bc / C, c = bc - b * C;
-  const int64_t R = 2LL * B * C;
-  const int64_t rre = (int64_t)(b * 2 + 0) * C + c;
-  const int64_t rim = (int64_t)(b * 2 + 1) * C + c;
-  for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-    const int mm = i / TKx, kk = i - mm * TKx;
-    const int k = k0 + kk, m = m0 + mm;
-    float2 n = make_float2(0.f, 0.f), q = n;
-    const int sl = (m < mact) ? (slab ? slab[m] : m) : -1;
-    if (k < g.Ke && sl >= 0) {
-      const float* src = Yt + (int64_t)sl * R * g.ldk;
-      const float2 e = make_float2(src[rre * g.ldk + k], src[rim * g.ldk + k]);
-      if (k < g.nh) {
-        const float2 o = make_float2(src[rre * g.ldk + g.ldke + k], src[rim * g.ldk + g.ldke + k]);
-        n = make_float2(e.x + o.x, e.y + o.y);
-        q = make_float2(e.x - o.x, e.y - o.y);
-      } else {
-        n = e;
-      }
-    }
-    tn[mm][kk] = n;
-    ts[mm][kk] = q;
-  }
-  __syncthreads();
-  float2* dst = Yn + (int64_t)bc * g.nlat * mmax;
-  for (int i = threadIdx.x; i < TKx * TMx; i += 256) {
-    const int kk = i / TMx, mm = i - kk * TMx;
-    const int k = k0 + kk, m = m0 + mm;
-    if (k >= g.Ke || m >= mmax) continue;
-    dst[(int64_t)k * mmax + m] = tn[mm][kk];
-    if (k < g.nh) dst[(int64_t)(g.nlat - 1 - k) * mmax + m] = ts[mm][kk];
-  }
-}
-
-template <int TKx, int TMx>
+// the inverse (and the band unpack): two-phase 32 x 128 tiles
 static void inv_sym_launch(const float* Yt, float2* Yn, int B, int C, const LatGeom& g, int mmax,
                            int mact, const int* perm, hipStream_t s) {
-  dim3 grid((unsigned)cdiv(g.Ke, TKx), (unsigned)cdiv(mmax, TMx), (unsigned)(B * C));
-  hipLaunchKernelGGL((transpose_inv_sym_kernel<TKx, TMx>), grid, dim3(256), 0, s, Yt, Yn, B, C,
-                     g, mmax, mact, perm);
-}
-
-static void inv_sym_dispatch(const float* Yt, float2* Yn, int B, int C, const LatGeom& g,
-                             int mmax, int mact, const int* perm, hipStream_t s) {
-  static const int t = tr_tile("MSFNO_TR_INV", 4);
-  switch (t) {
-    case 0: inv_sym_launch<64, 32>(Yt, Yn, B, C, g, mmax, mact, perm, s); break;
-    case 1: inv_sym_launch<TK_INV, TM_INV>(Yt, Yn, B, C, g, mmax, mact, perm, s); break;
-    case 2: inv_sym_launch<32, 128>(Yt, Yn, B, C, g, mmax, mact, perm, s); break;
-    case 4: {
-      const int nx = cdiv(g.Ke, 32), ny = cdiv(mmax, 128);
-      const int xr = tr_xcd(1);
-      const dim3 grid = tr_grid(xr, nx, ny, B * C);
-      static const bool bf = [] {
-        const char* e = getenv("MSFNO_TR_INV_BF");
-        return !(e && e[0] == '0');
-      }();
-      if (xr == 2 && bf)
-        hipLaunchKernelGGL((transpose_inv_sym2_kernel<32, 128, 2, true>), grid, dim3(256), 0, s,
-                           Yt, Yn, B, C, g, mmax, mact, perm, nx, ny);
-      else if (xr == 1)
-        hipLaunchKernelGGL((transpose_inv_sym2_kernel<32, 128, 1, false>), grid, dim3(256), 0, s,
-                           Yt, Yn, B, C, g, mmax, mact, perm, nx, ny);
-      else if (xr == 2)
-        hipLaunchKernelGGL((transpose_inv_sym2_kernel<32, 128, 2, false>), grid, dim3(256), 0, s,
-                           Yt, Yn, B, C, g, mmax, mact, perm, nx, ny);
-      else
-        hipLaunchKernelGGL((transpose_inv_sym2_kernel<32, 128, 0, false>), grid, dim3(256), 0, s, Yt,
-                           Yn, B, C, g, mmax, mact, perm, nx, ny);
-      break;
-    }
-    default: inv_sym_launch<16, 128>(Yt, Yn, B, C, g, mmax, mact, perm, s);
-  }
+  const int nx = cdiv(g.Ke, 32), ny = cdiv(mmax, 128);
+  hipLaunchKernelGGL((transpose_inv_sym2_kernel<32, 128, 2, true>), tr_grid(nx, ny, B * C),
+                     dim3(256), 0, s, Yt, Yn, B, C, g, mmax, mact, perm, nx, ny);
 }
 
 int launch_transpose_inv_sym(const float* Yt, float2* Yn, int B, int C, const LatGeom& g, int mmax,
                              int mact, hipStream_t s) {
-  inv_sym_dispatch(Yt, Yn, B, C, g, mmax, mact, nullptr, s);
+  inv_sym_launch(Yt, Yn, B, C, g, mmax, mact, nullptr, s);
   return launch_check("transpose_inv_sym");
 }
 
@@ -765,7 +459,7 @@ int launch_transpose_inv_sym(const float* Yt, float2* Yn, int B, int C, const La
 int launch_band_unpack(const float* recv, float2* Yn, int B, int C, const LatGeom& g, int mmax,
                        int mact, const int* perm, hipStream_t s) {
   if (!g.sym) return launch_transpose_inv(recv, Yn, B, C, g.nlat, mmax, mact, g.ldk, s, perm);
-  inv_sym_dispatch(recv, Yn, B, C, g, mmax, mact, perm, s);
+  inv_sym_launch(recv, Yn, B, C, g, mmax, mact, perm, s);
   return launch_check("band_unpack");
 }
 
@@ -1662,10 +1356,7 @@ __global__ __launch_bounds__(256) void compl_contract_dma_kernel(const float* __
 
 // MSFNO_CONTRACT_DMA=0 keeps the register-load kernel at batch 1 (A/B)
 static bool contract_dma() {
-  static const bool on = [] {
-    const char* e = getenv("MSFNO_CONTRACT_DMA");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = sw_on("MSFNO_CONTRACT_DMA");
   return on;
 }
 

@@ -1,7 +1,7 @@
 """DESIGN.md §9b lists exactly the run-time switches the sources read.
 
-A switch is an `MSFNO_*` name passed to getenv() in csrc/ (directly, or to a helper
-listed in GETENV that forwards it) or read from os.environ in msfno_amd/.  Status codes
+A switch is an `MSFNO_*` name passed to one of the readers of csrc/switches.h (GETENV;
+the header holds the only getenv() of csrc/) or read from os.environ in msfno_amd/.  Status codes
 (`MSFNO_OK`, ...) and bench.py's `MSFNO_BENCH_*` names are not switches: neither is read from the environment by the library."""
 import glob
 import os
@@ -10,8 +10,9 @@ import re
 from conftest import PKG_DIR, REPO
 
 NAME = r"MSFNO_[A-Z0-9_]+"
-# getenv and the helpers that hand their first argument to it (spectral.hip tr_tile)
-GETENV = ("getenv", "tr_tile")
+# the readers of csrc/switches.h: each hands its first argument to the one getenv()
+GETENV = ("sw_raw", "sw_set", "sw_char", "sw_on", "sw_is1", "sw_is1_or", "sw_eq", "sw_int")
+SWITCHES_H = "switches.h"
 
 
 def _read(path):
@@ -19,11 +20,15 @@ def _read(path):
         return fh.read()
 
 
+def _csrc_files():
+    return [f for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*"))
+            if os.path.isfile(f) and f.endswith((".hip", ".cpp", ".h"))]
+
+
 def source_switches():
     names = set()
-    for f in glob.glob(os.path.join(PKG_DIR, "csrc", "*")):
-        if os.path.isfile(f) and f.endswith((".hip", ".cpp", ".h")):
-            names |= set(re.findall(r'\b(?:%s)\(\s*"(%s)"' % ("|".join(GETENV), NAME), _read(f)))
+    for f in _csrc_files():
+        names |= set(re.findall(r'\b(?:%s)\(\s*"(%s)"' % ("|".join(GETENV), NAME), _read(f)))
     for f in glob.glob(os.path.join(PKG_DIR, "msfno_amd", "**", "*.py"), recursive=True):
         names |= set(re.findall(r'os\.environ(?:\.get\(|\[)\s*"(%s)"' % NAME, _read(f)))
     return {n for n in names if not n.startswith("MSFNO_BENCH_")}
@@ -38,6 +43,13 @@ def table_switches():
         if line.startswith("| `MSFNO_"):
             names |= set(re.findall(NAME, line.split("|")[1]))
     return names
+
+
+def test_only_the_switch_header_calls_getenv():
+    assert "getenv(" in _read(os.path.join(PKG_DIR, "csrc", SWITCHES_H))
+    others = [os.path.basename(f) for f in _csrc_files()
+              if os.path.basename(f) != SWITCHES_H and "getenv(" in _read(f)]
+    assert not others, f"getenv( outside csrc/{SWITCHES_H}: {others}"
 
 
 def test_sources_read_switches_at_all():
