@@ -853,7 +853,11 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * WV;
   const int YB = mmax * 8;
-  const int64_t yend = (((int64_t)rows * YB) & ~(int64_t)15) - 16;  // last chunk inside Yn
+  // the last 16-B chunk that starts inside Yn.  With rows * mmax odd it holds Yn's last bin
+  // and 8 bytes behind it: Yn is 16-B aligned (launch_c2r), so the chunk stays in Yn's last
+  // page, and no bin k >= mmax is used.  (Clamping to the last chunk wholly inside Yn gave
+  // the last row's last bin the value two bins before it.)
+  const int64_t yend = ((int64_t)rows * YB - 1) & ~(int64_t)15;
   auto issue_y = [&](int64_t r, int sl) {
     const int64_t a0 = ((int64_t)r * YB) & ~(int64_t)15;
     const char* src = reinterpret_cast<const char*>(in);
@@ -1141,7 +1145,9 @@ static int launch_c2r(const FFTArgs& a, const float2* in, float* x, const float*
     const int ncy = (mmax * 8 + 16 + 1023) / 1024;
     C2RPlanes pp{};
     if (planes) pp = *planes;
-    if (use_fft_dma() && (2 * CL::H) % 8 == 0 && mmax <= CL::H + 1 && ncy <= 5) {
+    // (Yn rows are staged in 16-B chunks counted from `in`: it must be 16-B aligned)
+    if (use_fft_dma() && (2 * CL::H) % 8 == 0 && mmax <= CL::H + 1 && ncy <= 5 &&
+        (reinterpret_cast<uintptr_t>(in) & 15) == 0) {
       const int rb = 2 * CL::H * 4, nca = (rb + 1023) / 1024;
       // one row ahead, 4-wave workgroups, as many per CU as the LDS holds
       // skip rows through registers (no LDS slot): 16 waves per CU instead of 10,
