@@ -33,7 +33,11 @@ __device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds) {
 }
 
 // one wave-instruction, SADDR form: lane l copies 16 B from sbase + voff (lane's 32-bit
-// byte offset) to LDS byte lds + 16 l (sbase, lds wave-uniform)
+// byte offset) to LDS byte lds + 16 l (sbase, lds wave-uniform).  The single piece of
+// the kernels that spread a refill under their MFMAs (gemm_x6c.hip, skip_hp_kernel): no
+// 64-bit VALU address per piece.  It saves and restores M0 itself: between two asm
+// statements M0 belongs to the compiler, so pieces with MFMAs between them cannot share
+// one save / restore the way the pieces of glds16x4 / glds16x6 do inside one statement.
 __device__ __forceinline__ void glds16s(uint64_t sbase, uint32_t voff, uint32_t lds) {
   unsigned keep;
   sbase = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(sbase >> 32)) << 32) |

@@ -23,6 +23,8 @@
 #include "dma.h"
 #include "gemm_common.h"
 
+#include <type_traits>
+
 namespace msfno {
 
 // NP planes per value (split_engine.h): 3 = the x6 engine, 2 = the x3h engine (operands
@@ -218,58 +220,67 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   const int tm = lin % p.tiles_m, tn = lin / p.tiles_m;
   const int z = blockIdx.z;
   const int m0 = tm * BM, n0 = tn * BN;
-  const int K = p.ci, N = p.N, ldx = p.ldx;
+  const int K = p.ci, N = p.N;
   const int nk = (K + BK - 1) / BK;
   const unsigned short* X = p.X + z * p.x_b;
 
   // LDS-DMA pieces c = wave + NW q (q < NPC): c < APC -> A (matrix-plane c / 4, rows
   // 32 (c % 4) ..), else B (matrix-plane (c - APC) / 4, k rows 4 ((c - APC) % 4) ..)
-  const unsigned short* src[NPC];
+  // Each piece is addressed as a wave-uniform base that advances with the k-tile (A: the
+  // weight image; B: this column tile's planes, tiled layout) plus the lane's 32-bit byte
+  // offset voff, computed once (the hosts check that the weight image stays below 4 GB).
+  static_assert(BF32 || (LAY & 1) != 0, "DMA-fed B planes come in the tiled layout");
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  uint32_t voff[NPC];
   int dst[NPC];
-  int brow[NPC];  // B: k row of this lane within the k-tile (-1 for A pieces)
+  int kind[NPC];  // wave-uniform: 0 = A piece, 1 = B piece, -1 = none (BF32: no B pieces)
 #pragma unroll
   for (int q = 0; q < NPC; ++q) {
-    const int c = wave + NW * q;
-    if (BF32 && c >= APC) {  // no B pieces; this slot idles
-      src[q] = nullptr;
+    const int c = wave_u + NW * q;
+    if (BF32 && c >= APC) {
+      voff[q] = 0;
       dst[q] = 0;
-      brow[q] = -2;
+      kind[q] = -1;
     } else if (c < APC) {
       const int mp = c / (BM / 32), mb = c % (BM / 32);
       const int mat = mp / NP, pl = mp - NP * mat;
       const int m = 32 * mb + (lane >> 1);
       const int h = (lane & 1) ^ ((m >> 3) & 1);
-      src[q] = p.Aw + mat * p.a_mat + pl * p.a_plane + (int64_t)(m0 + m) * 16 + 8 * h;
+      voff[q] = (uint32_t)((mat * p.a_mat + pl * p.a_plane + (int64_t)(m0 + m) * 16 + 8 * h) * 2);
       dst[q] = mp * A_PLANE + mb * 32 * BK;
-      brow[q] = -1;
+      kind[q] = 0;
     } else {
       const int cb = c - APC;
       const int mp = cb >> 2, rq = cb & 3;
-      const int mat = mp / NP, pl = mp - NP * mat;
-      const int row = 4 * rq + (lane >> 4);
-      const int gu = (lane & 15) ^ (4 * (row & 3));
-      if constexpr ((LAY & 1) != 0)
-        src[q] = X + ((int64_t)tn * p.kt_in * NMP + mp) * B_PLANE + rq * 4 * BN + 8 * (lane & 15) +
-                 BN * (lane >> 4);
-      else
-        src[q] = X + mat * p.x_mat + pl * p.x_plane + min(n0 + 8 * gu, ldx - 8);
+      voff[q] = (uint32_t)((mp * B_PLANE + rq * 4 * BN + 8 * (lane & 15) + BN * (lane >> 4)) * 2);
       dst[q] = A_ALL + mp * B_PLANE + rq * 4 * BN;
-      brow[q] = row;
+      kind[q] = 1;
     }
   }
-  const int64_t a_kstride = (int64_t)p.Mp * 16;
+  const uint64_t a_base = reinterpret_cast<uint64_t>(p.Aw), a_kbytes = (uint64_t)p.Mp * 16 * 2;
+  const uint64_t b_base =
+      BF32 ? 0 : reinterpret_cast<uint64_t>(X + (int64_t)tn * p.kt_in * NMP * B_PLANE);
+  constexpr uint64_t b_kbytes = (uint64_t)NMP * B_PLANE * 2;
   const uint32_t ring_lds = lds_addr(ring);
+  // the wave-uniform part of a refill (k-tile kt into stage st), once per k-tile
+  struct Refill {
+    uint64_t a, b;
+    uint32_t lds;
+  };
+  auto refill_of = [&](int kt, int st) {
+    return Refill{a_base + kt * a_kbytes, b_base + kt * b_kbytes,
+                  ring_lds + (uint32_t)(st * STAGE * 2)};
+  };
+  // its piece q
+  auto issue_piece = [&](const Refill& r, int q) {
+    if (BF32 && kind[q] < 0) return;
+    glds16s(kind[q] == 0 ? r.a : r.b, voff[q], r.lds + (uint32_t)(dst[q] * 2));
+  };
+  // a whole k-tile at once (the prologue: no MFMAs to issue it under)
   auto issue = [&](int kt, int st) {
-    const uint32_t base = ring_lds + (uint32_t)(st * STAGE * 2);
+    const Refill r = refill_of(kt, st);
 #pragma unroll
-    for (int q = 0; q < NPC; ++q) {
-      if (BF32 && brow[q] == -2) continue;
-      const unsigned short* g = brow[q] < 0
-                                    ? src[q] + kt * a_kstride
-                                    : ((LAY & 1) ? src[q] + (int64_t)kt * NMP * B_PLANE
-                                                 : src[q] + (int64_t)min(kt * BK + brow[q], K - 1) * ldx);
-      glds16(g, base + (uint32_t)(dst[q] * 2));
-    }
+    for (int q = 0; q < NPC; ++q) issue_piece(r, q);
   };
   // BF32 B staging: thread -> (k row, 4 columns); NW * 64 threads cover 16 x 128
   static_assert(!BF32 || NW * 64 * 4 == BK * BN, "BF32 staging: one float4 per thread");
@@ -341,34 +352,54 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
     const int c = wn * WN + j * 32 + 16 * g16 + 4 * (li & 3);
     b_off[j] = A_ALL + br * BN + (((c >> 3) ^ (4 * (br & 3))) << 3) + (c & 7);
   }
-  auto mfma_tile = [&](int st) {
+  // The MFMAs of one k-tile as NG groups (matrix mat, column tile j: MT x NP-engine
+  // products), each accumulator seeing its products k-tile by k-tile in engine order.  The
+  // fragments of group g + 1 are read before the MFMAs of group g, and after(g) runs
+  // behind them: the k-loops put the next refill's DMA pieces there.  (A DMA piece is
+  // an asm statement the compiler moves no LDS read across, so the read-ahead is
+  // written out here and not left to the scheduler.)
+  constexpr int NG = 3 * NT;
+  auto mfma_tile = [&](int st, auto&& after) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const unsigned short* base = ring + st * STAGE;
+    Frag a[2][MT][NP], b[2][NP];
+    auto read_frags = [&](int g) {
+      const int mat = g / NT, j = g % NT;
+      if (j == 0) {
 #pragma unroll
-    for (int mat = 0; mat < 3; ++mat) {
-      Frag a[MT][NP];
+        for (int i = 0; i < MT; ++i)
 #pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl)
-          a[i][pl] = *reinterpret_cast<const Frag*>(base + (mat * NP + pl) * A_PLANE + a_off[i]);
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        Frag b[NP];
-#pragma unroll
-        for (int pl = 0; pl < NP; ++pl) {
-          const unsigned short* q = base + (mat * NP + pl) * B_PLANE + b_off[j];
-          const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)q));
-          const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(q + 4 * BN)));
-          const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-          b[pl] = __builtin_bit_cast(Frag, v);
-        }
-#pragma unroll
-        for (int i = 0; i < MT; ++i) SplitEng<NP>::mma(a[i], b, acc[mat][i][j]);
+          for (int pl = 0; pl < NP; ++pl)
+            a[mat & 1][i][pl] =
+                *reinterpret_cast<const Frag*>(base + (mat * NP + pl) * A_PLANE + a_off[i]);
       }
+#pragma unroll
+      for (int pl = 0; pl < NP; ++pl) {
+        const unsigned short* q = base + (mat * NP + pl) * B_PLANE + b_off[j];
+        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)q));
+        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(q + 4 * BN)));
+        const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+        b[g & 1][pl] = __builtin_bit_cast(Frag, v);
+      }
+    };
+    read_frags(0);
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      const int mat = g / NT, j = g % NT;
+      if (g + 1 < NG) read_frags(g + 1);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) SplitEng<NP>::mma(a[mat & 1][i], b[g & 1], acc[mat][i][j]);
+      after(g);
     }
+  };
+  // piece q of a k-tile's NPC goes behind group q * NG / NPC: in order, spread evenly,
+  // the first one behind the first group's MFMAs
+  auto refill_after = [&](int g, const Refill& r) {
+#pragma unroll
+    for (int q = 0; q < NPC; ++q)
+      if (q * NG / NPC == g) issue_piece(r, q);
   };
 
   issue(0, 0);
@@ -381,36 +412,68 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   }
   if constexpr (NS == 3) {
     // k-tiles kt and kt + 1 in flight at the top of iteration kt: wait for kt only
-    // (NPC DMA instructions per wave and k-tile), then refill the stage kt - 1 left
-    for (int kt = 0; kt < nk; ++kt) {
+    // (NPC DMA instructions per wave and k-tile), then refill the stage kt - 1 left,
+    // its NPC pieces spread behind the MFMA groups of this k-tile.
+    //   WAR   stage (kt + 2) % 3 = (kt - 1) % 3 was last read in iteration kt - 1; every
+    //         wave retired those reads (lgkmcnt(0)) before this iteration's barrier, and
+    //         every piece follows the barrier in program order.
+    //   RAW   k-tile kt + 2 is first read in iteration kt + 2, after that iteration's wait
+    //         (vmcnt(NPC), or vmcnt(0) for the last: the wave's own pieces of kt + 2 are
+    //         then retired, only those of kt + 3 may be younger) and barrier (the others').
+    //   count the waits assume NPC DMA instructions per wave and k-tile, issued in k-tile
+    //         order and all before the next iteration's wait; the loop issues no other
+    //         vector-memory instruction (the epilogue's come after vmcnt(0)).
+    // (the iterations that refill and the last two that do not are separate loops, so a
+    // piece carries no branch)
+    auto step = [&](int kt, auto more_c) {
+      constexpr bool MORE = decltype(more_c)::value;
       if (kt + 1 < nk)
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPC) : "memory");
       else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
-      if (kt + 2 < nk) issue(kt + 2, (kt + 2) % 3);
+      const Refill r = refill_of(kt + 2, (kt + 2) % 3);
       __builtin_amdgcn_s_setprio(1);
-      mfma_tile(kt % 3);
+      mfma_tile(kt % 3, [&](int g) {
+        if constexpr (MORE) refill_after(g, r);
+      });
       __builtin_amdgcn_s_setprio(0);
-    }
+    };
+    int kt = 0;
+    for (; kt + 2 < nk; ++kt) step(kt, std::true_type{});
+    for (; kt < nk; ++kt) step(kt, std::false_type{});
   } else {
-    for (int kt = 0; kt < nk; ++kt) {
+    // Two stages, one k-tile in flight; the refill of stage (kt + 1) & 1 is spread behind
+    // the MFMA groups of k-tile kt.
+    //   WAR   stage (kt + 1) & 1 was last read in iteration kt - 1 (MFMA fragments; BF32:
+    //         last written by store_bf of iteration kt - 2); lgkmcnt(0) and this
+    //         iteration's barrier come before every piece and before store_bf(kt + 1).
+    //   RAW   k-tile kt + 1 is read in iteration kt + 1, after its vmcnt(0) (every piece of
+    //         the wave, and the BF32 fp32 loads) and barrier.
+    //   count vmcnt(0) only: nothing depends on the order of the pieces and the BF32
+    //         loads of load_bf, which now go first so their latency has the whole k-tile.
+    auto step = [&](int kt, auto more_c) {
+      constexpr bool MORE = decltype(more_c)::value;
       if constexpr ((DBG & 1) == 0)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my DMA of k-tile kt landed
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // everyone's landed; stage (kt + 1) & 1 is free
-      if (kt + 1 < nk) {
-        if constexpr ((DBG & 2) == 0) issue(kt + 1, (kt + 1) & 1);
-        if constexpr (BF32) load_bf(kt + 1);  // after the DMA: in-order vmcnt
-      }
+      const Refill r = refill_of(kt + 1, (kt + 1) & 1);
+      if constexpr (BF32 && MORE) load_bf(kt + 1);
       __builtin_amdgcn_s_setprio(1);
-      if constexpr ((DBG & 4) == 0) mfma_tile(kt & 1);
-      __builtin_amdgcn_s_setprio(0);
-      if constexpr (BF32) {
-        if (kt + 1 < nk) store_bf(kt + 1, (kt + 1) & 1);
+      if constexpr ((DBG & 4) == 0) {
+        mfma_tile(kt & 1, [&](int g) {
+          if constexpr (MORE && (DBG & 2) == 0) refill_after(g, r);
+        });
+      } else if constexpr (MORE && (DBG & 2) == 0) {
+        issue(kt + 1, (kt + 1) & 1);
       }
-    }
+      __builtin_amdgcn_s_setprio(0);
+      if constexpr (BF32 && MORE) store_bf(kt + 1, (kt + 1) & 1);
+    };
+    for (int kt = 0; kt + 1 < nk; ++kt) step(kt, std::true_type{});
+    if (nk > 0) step(nk - 1, std::false_type{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -505,6 +568,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
 
 // ---- host ---------------------------------------------------------------------
 
+// the kernel addresses the A pieces by 32-bit byte offsets into the layer's weight image
+// (three matrices of a_mat 16-bit elements)
+static bool x6c_image_fits(const X6CParams& p) { return 3 * p.a_mat * 2 < (1LL << 32); }
+
 size_t gemm_x6c_weight_bytes(int co, int ci) {
   const int64_t Mp = round_up(co, X6C_BM), Kp = round_up(ci, X6C_BK);
   return (size_t)round_up(3 * 3 * Mp * Kp * 2, 256);
@@ -541,6 +608,7 @@ int gemm_x6c_f32b(const unsigned short* Aw, int co, int ci, const float* Sin, in
   p.Aw = Aw;
   p.a_plane = (int64_t)p.Mp * KT * 16;
   p.a_mat = 3 * p.a_plane;
+  MSFNO_REQUIRE(x6c_image_fits(p), MSFNO_EINVAL, "gemm_x6c: weight image of 4 GB or more");
   p.Xf = Sin;
   p.xf_b = 2LL * ci * ldSin;
   p.xf_im = (int64_t)ci * ldSin;
@@ -581,6 +649,7 @@ int gemm_x6c(const unsigned short* Aw, int co, int ci, const unsigned short* X, 
   p.Aw = Aw;
   p.a_plane = (int64_t)p.Mp * KT * 16;
   p.a_mat = 3 * p.a_plane;
+  MSFNO_REQUIRE(x6c_image_fits(p), MSFNO_EINVAL, "gemm_x6c: weight image of 4 GB or more");
   p.X = X;
   p.x_plane = (int64_t)ci * ldx;
   p.x_mat = 3 * p.x_plane;
@@ -705,6 +774,7 @@ int gemm_x3c(const unsigned short* Aw, int co, int ci, const float* Sin, int ldS
   p.Aw = Aw;
   p.a_plane = (int64_t)p.Mp * KT * 16;
   p.a_mat = 2 * p.a_plane;
+  MSFNO_REQUIRE(x6c_image_fits(p), MSFNO_EINVAL, "gemm_x3c: weight image of 4 GB or more");
   p.Xf = Sin;
   p.xf_b = 2LL * ci * ldSin;
   p.xf_im = (int64_t)ci * ldSin;

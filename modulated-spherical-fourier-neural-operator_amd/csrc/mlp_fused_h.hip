@@ -321,6 +321,9 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     __builtin_amdgcn_s_barrier();
     return ring + (q % NS) * MH_SLICE;
   };
+  // (the refill stays one burst after the step's first MFMAs: spread over the step as four
+  // single pieces it measured 1.964 against 1.970 ms in-block, inside the run-to-run
+  // spread, profiles/r09_refill/ab4_table.txt)
   auto refill = [&](int q) {
     if (q >= 1 && q + NS - 1 < MH_NSLICE) issue(q + NS - 1);
   };
@@ -654,6 +657,9 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
   for (int ot = 0; ot < 16; ++ot) oacc[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
   const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
 
+  // (the refill stays one burst: as four spread pieces the kernel alone measured 1.598
+  // against 1.611 ms at config 2, 0.8 %, under twice the parent's own 0.44 % spread,
+  // profiles/r09_refill/skip_h_alone.txt)
 #pragma unroll
   for (int q = 0; q < SK_NSLICE; ++q) {
     // slice q landed (up to NS - 2 later slices may stay in flight); slot of q - 1 free
@@ -717,6 +723,18 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
 // steps of a tile (tile 0: those groups were drained in the prologue).  The tail
 // issues dummy groups (the last tile again) so the counts stay exact, and the kernel
 // drains every DMA before it exits.
+//
+// Within a step the group's six DMAs are spread, one after each of the MFMA pairs
+// u = 0..5 (the prologue's NS - 1 groups stay bursts: there are no MFMAs yet):
+//   WAR   group n + NS - 1 refills slot (n - 1) % NS, last read (weights and x piece) in
+//         step n - 1; those reads are retired (lgkmcnt(0)) before step n's barrier, which
+//         every DMA of the step follows in program order.
+//   RAW   the group is first read in step n + NS - 1, after that step's counted wait (the
+//         wave's own six) and barrier (the other waves').
+//   count six VMEM instructions per wave and step in the order w0..w3, x0, x1, all issued
+//         before the next step's wait; a tile's 32 output stores still come after the
+//         sixth DMA of its step 15 and before the first wait of the next tile, so
+//         vmcnt(50) / vmcnt(18) count what they counted.
 constexpr int SP_NS = 5, SP_W = 4, SP_PX = 32 * SP_W;
 constexpr int SP_XPAIR = 1024 + 32;                  // two 512-B x rows + bank pad
 constexpr int SP_WBYTES = MH_SLICE * 2;              // 16 KB of weights
@@ -808,6 +826,22 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2)
       glds16s(xq, sr.xo[h2], slot + (uint32_t)(SP_WBYTES + (2 * wave_u + h2) * SP_XPAIR));
+  };
+  // DMA k (0..SP_GROUP - 1) of issue(sr, n, q) on its own: 0..3 the weight pieces, 4 and 5
+  // the x row pairs, in the order of the group above
+  auto issue_piece = [&](const Src& sr, int n, int q, int k) {
+    const uint32_t slot = ring_lds + (uint32_t)((n % NS) * SP_SLOT);
+    if (k < 4) {
+      uint64_t wb = sr.w;
+      asm volatile("" : "+s"(wb));
+      glds16s(wb + (uint64_t)q * MH_SLICE * 2 + (uint64_t)(k * 4096), w_voff,
+              slot + (uint32_t)(k * 4096 + wave_u * 1024));
+    } else {
+      uint64_t xb0 = sr.x, p4 = (uint64_t)P * 4;
+      asm volatile("" : "+s"(xb0), "+s"(p4));
+      glds16s(xb0 + (uint64_t)(32 * (q >> 1) + 4 * (q & 1)) * p4, sr.xo[k - 4],
+              slot + (uint32_t)(SP_WBYTES + (2 * wave_u + (k - 4)) * SP_XPAIR));
+    }
   };
 
   int zc = t0 / tpf, zx = (ntile > 1 ? t0 + 1 : t0) / tpf;
@@ -923,9 +957,9 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
 #pragma unroll
         for (int pg = 0; pg < 2; ++pg)
           SplitEng<2>::mma(a[u % 3], xf[pg][kh * 4 + (u >> 1)], oacc[pg][2 * j + (u & 1)]);
-        if (u == 0) {
-          if (q + NS - 1 < SK_NSLICE) issue(s_cur, n + NS - 1, q + NS - 1);
-          else issue(s_nxt, n + NS - 1, q + NS - 1 - SK_NSLICE);
+        if (u < SP_GROUP) {  // DMA u of group n + NS - 1, after the step's MFMA triples 2u, 2u + 1
+          if (q + NS - 1 < SK_NSLICE) issue_piece(s_cur, n + NS - 1, q + NS - 1, u);
+          else issue_piece(s_nxt, n + NS - 1, q + NS - 1 - SK_NSLICE, u);
         }
       }
     }
