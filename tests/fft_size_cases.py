@@ -42,7 +42,9 @@ GPU_BAR = 2e-6            # the transform parity bar of test_gpu_parity.py, here
 DEGREE_BAND = 2           # degrees per order in the inverse transform's input
 COLUMN_FLOOR = 0.05       # smallest column maximum / largest column maximum of a reference
 
-Case = namedtuple("Case", "nlat nlon mmax")
+# lead: the leading dimensions of the case's fields; the sweep of the compiled codelets
+# (fft_codelet_cases.py) varies it, the cases below all use LEAD
+Case = namedtuple("Case", "nlat nlon mmax lead", defaults=(LEAD,))
 
 
 def _full(nlat, nlon):
@@ -91,7 +93,7 @@ def dense_table(case, inverse):
 @functools.lru_cache(maxsize=None)
 def forward_input(case):
     g = torch.Generator().manual_seed(_seed(case, 1))
-    return torch.randn(*LEAD, case.nlat, case.nlon, generator=g)
+    return torch.randn(*case.lead, case.nlat, case.nlon, generator=g)
 
 
 @functools.lru_cache(maxsize=None)
@@ -120,7 +122,7 @@ def inverse_input(case, kind):
     last leaves the fp32 restatement under a quarter of the bar.  The Legendre stage's own
     parity on full noise is test_gpu_parity.py's and the boundary test's business."""
     g = torch.Generator().manual_seed(_seed(case, 2))
-    a = torch.view_as_complex(torch.randn(*LEAD, case.mmax, case.mmax, 2, generator=g))
+    a = torch.view_as_complex(torch.randn(*case.lead, case.mmax, case.mmax, 2, generator=g))
     a = a / a.abs()
     d = torch.arange(case.mmax)[:, None] - torch.arange(case.mmax)[None, :]   # l - m
     band = (d >= 0) & (d < DEGREE_BAND)                                       # [l, m]

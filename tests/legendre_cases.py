@@ -281,54 +281,123 @@ BLOCK_IDS = [block_id(c) for c in BLOCK_CASES]
 assert len(set(BLOCK_IDS)) == len(BLOCK_IDS)
 
 
+def nlon_of(c):
+    """The grid width of a block case: NLON, unless the case has a field of its own
+    (fft_codelet_cases.py)."""
+    return getattr(c, "nlon", NLON)
+
+
 def block_cfg(c):
-    return sfno_ref.BlockCfg(filter_type=c.filter, inner_skip=None, outer_skip=None,
-                             has_mlp=False, spectral_layers=3)
+    """No inner skip, MLP or outer skip, unless the case has fields `skip` / `mlp`
+    (fft_codelet_cases.py)."""
+    return sfno_ref.BlockCfg(filter_type=c.filter, inner_skip=getattr(c, "skip", None),
+                             outer_skip=None, has_mlp=getattr(c, "mlp", False),
+                             spectral_layers=3)
+
+
+FILTER_TO_SKIP = 2.0                      # standard deviation of the filter's output / the skip's
 
 
 @functools.lru_cache(maxsize=None)
 def block_params(c):
-    return sfno_ref.make_block_params(c.C, c.lmax, c.mmax, block_cfg(c), seed=_seed(c, 7) % 9973,
-                                      randomize_affine=True)
+    p = sfno_ref.make_block_params(c.C, c.lmax, c.mmax, block_cfg(c), seed=_seed(c, 7) % 9973,
+                                   randomize_affine=True)
+    if block_cfg(c).inner_skip is not None:
+        _balance_filter(c, p)
+    return p
+
+
+def _balance_filter(c, p):
+    """Scales the filter's last (linear) weight by a power of two so that the filter's output
+    has about FILTER_TO_SKIP times the standard deviation of the inner skip's (per channel,
+    means removed).  With the initialisation's 0.02-weights the filter adds between 0.002 and
+    17 times the skip, depending on filter, width and depth: where it adds next to nothing,
+    no error of the transforms reaches the block's output."""
+    cfg = block_cfg(c)
+    q = {k: (v.double() if v.is_floating_point() else v) for k, v in p.items()}
+    x = block_input(c).double()
+    sht = _Transform(table(c, False), False, c.mmax, None, nlon_of(c))
+    isht = _Transform(table(c, True), True, c.mmax, nlon=nlon_of(c))
+    with torch.no_grad():
+        xn = sfno_ref.instance_norm(x, q["norm0.weight"], q["norm0.bias"], cfg.eps)
+        if c.filter == NL:
+            name = "filter_layer.filter.wout"
+            ws = [q[f"filter_layer.filter.w.{i}"] for i in range(cfg.spectral_layers)]
+            f = sfno_ref.spectral_attention_s2(xn, sht, isht, ws, q[name])
+        else:
+            name = "filter_layer.filter.w"
+            f = sfno_ref.spectral_conv_s2(xn, sht, isht, q[name], q["filter_layer.filter.ii"],
+                                          q["filter_layer.filter.jj"])
+        s = x
+        if cfg.inner_skip == "linear":
+            s = sfno_ref.conv1x1(x, q["inner_skip.weight"], q["inner_skip.bias"])
+    dev = lambda t: (t - t.mean((-2, -1), keepdim=True)).std().item()
+    p[name] = p[name] * 2.0 ** round(torch.log2(torch.tensor(FILTER_TO_SKIP * dev(s) / dev(f))).item())
 
 
 @functools.lru_cache(maxsize=None)
 def block_input(c):
     g = torch.Generator().manual_seed(_seed(c, 11) + c.B)
-    return torch.randn(c.B, c.C, c.nlat, NLON, generator=g)
+    x = torch.randn(c.B, c.C, c.nlat, nlon_of(c), generator=g)
+    if getattr(c, "wave1", 0.0):
+        # a zonal-wavenumber-1 wave, its profile in latitude half even, half odd about the
+        # equator, its amplitude 0.5 .. 1.5 wave1 by channel: order 1 holds a fixed share of
+        # the field's energy however many orders the grid has (every other order keeps its
+        # O(1) weight), so MUTATED_BIN stays visible at mmax of several hundred
+        phi = 2.0 * torch.pi * torch.arange(nlon_of(c)) / nlon_of(c)
+        amp = (0.5 + torch.rand(c.B, c.C, 1, 1, generator=g)) * c.wave1
+        prof = 0.5 + torch.linspace(-1.0, 1.0, c.nlat)[:, None]
+        x = x + amp * prof * torch.cos(phi + 0.3)
+        # ... and a second wave of the same amplitude at a high order (fft_codelet_cases.py:
+        # in the last KiB or two of spectrum that the inverse FFT stages per row)
+        if getattr(c, "wave_hi", 0):
+            x = x + amp * prof.flip(0) * torch.cos(c.wave_hi * phi + 1.1)
+    if getattr(c, "offset", False):
+        # every channel's mean 30 .. 100 standard deviations from zero, either sign
+        u = torch.rand(c.C, generator=g)
+        sign = 1.0 - 2.0 * (torch.arange(c.C) % 2)
+        x = x + (sign * (30.0 + 70.0 * u))[None, :, None, None]
+    return x
 
 
 class _Transform:
     """A transform of the oracle by its definition on a given table (the oracle's own
     modules would build a max(lmax, mmax)^2 nlat recurrence table first)."""
 
-    def __init__(self, tab, inverse, mmax, mutate=None):
-        self.inverse, self.mmax, self.mutate = inverse, mmax, mutate
+    def __init__(self, tab, inverse, mmax, mutate=None, nlon=NLON):
+        self.inverse, self.mmax, self.mutate, self.nlon = inverse, mmax, mutate, nlon
         self.weights = self.pct = tab
 
     def __call__(self, x):
         if self.inverse:
-            return F._inverse(x, self.pct, NLON)
+            return F._inverse(x, self.pct, self.nlon)
         a = F._forward(x, self.weights, self.mmax)
         if self.mutate is not None:
             m, p = self.mutate
             a = a.clone()
-            a[0, :, m + p::2, m] *= MUTATION
+            if p is None:                 # the whole Fourier bin m
+                a[0, :, :, m] *= MUTATION
+            else:
+                a[0, :, m + p::2, m] *= MUTATION
         return a
 
 
 def _oracle(c, dtype, mutate=None):
     p = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in block_params(c).items()}
     x = block_input(c).to(dtype)
-    sht = _Transform(table(c, False).to(dtype), False, c.mmax, mutate)
-    isht = _Transform(table(c, True).to(dtype), True, c.mmax)
+    sht = _Transform(table(c, False).to(dtype), False, c.mmax, mutate, nlon_of(c))
+    isht = _Transform(table(c, True).to(dtype), True, c.mmax, nlon=nlon_of(c))
+    cfg = block_cfg(c)
     with torch.no_grad():
-        return sfno_ref.global_conv(p, x, x, sht, isht, block_cfg(c))
+        if cfg.has_mlp:                   # the whole block, no FiLM (fft_codelet_cases.py)
+            return sfno_ref.block_forward(p, x, sht, isht, cfg)
+        return sfno_ref.global_conv(p, x, x, sht, isht, cfg)
 
 
 @functools.lru_cache(maxsize=None)
 def block_reference(c):
-    """fp64 (B, C, nlat, nlon) global_conv of the oracle."""
+    """fp64 (B, C, nlat, nlon) global_conv (block_forward for a case with an MLP) of the
+    oracle."""
     return _oracle(c, torch.float64)
 
 
@@ -346,7 +415,10 @@ def block_bar(c):
 MUTATED_BLOCK = (1, 1)                    # (m, parity): the odd degrees of order 1, batch element 0
 
 
-def block_mutation_shift(c):
+MUTATED_BIN = (1, None)                   # all degrees of order 1 (the FFT's bin 1), batch element 0
+
+
+def block_mutation_shift(c, block=MUTATED_BLOCK):
     """How far the fp64 oracle moves when one (m, parity) block of batch element 0's forward
     coefficients is scaled by MUTATION."""
-    return (_oracle(c, torch.float64, MUTATED_BLOCK) - block_reference(c)).abs().max().item()
+    return (_oracle(c, torch.float64, block) - block_reference(c)).abs().max().item()
