@@ -83,6 +83,45 @@ int msfno_sht_inverse(msfno_sht_plan_t plan, const float* in, float* x, int bc,
                       void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Vector spherical harmonic transforms (torch_harmonics RealVectorSHT /
+ * InverseRealVectorSHT; the reference forecasts 30 wind components and never transforms
+ * them; the Python mirror is msfno_amd/harmonics/vector.py).  A tangent field has the
+ * components (v_θ, v_φ), southward and eastward; s is its spheroidal coefficient (of
+ * ∇Y_lm) and t its toroidal one (of r̂ × ∇Y_lm).  With D_l^m = dP̄_l^m/dθ,
+ * Q_l^m = m P̄_l^m / sin θ and the scalar transforms' longitude step, per m:
+ *   synthesis  v_θ = Σ_l D s - i Q t,              v_φ = Σ_l i Q s + D t
+ *   analysis   s = 1/(l(l+1)) Σ_k w_k [D v_θ - i Q v_φ],  t = 1/(l(l+1)) Σ_k w_k [i Q v_θ + D v_φ]
+ * with s = t = 0 at l = 0 and where l < m.
+ *
+ * msfno_vector_legendre_table: table (2, mmax, lmax, nlat) float64, [0] = D, [1] = Q,
+ * colatitudes north->south, normalisation and phase of msfno_legendre_table; inverse == 0
+ * multiplies both by w_k / (l(l+1)) (the l = 0 row is zero), inverse == 1 leaves them bare.
+ * Rows l < m are zero; no step divides by sin θ, so the pole columns are exact (zero but for
+ * m = 1, where D = Q).
+ *
+ * A vector transform runs on two scalar plans of its direction, made and loaded by
+ * msfno_sht_plan_create / msfno_sht_plan_load_table:
+ *   plan_d  lmax + 1 degrees, table row l + 1 = D_l (row 0 zero): moved up one degree, D has
+ *           the equatorial parity of a scalar table and takes the hemisphere-folded path;
+ *   plan_q  lmax degrees, table Q.
+ * v (bc, 2, nlat, nlon) fp32, st (bc, 2, lmax, mmax) complex64 interleaved, [.][0] = s and
+ * [.][1] = t; every word of the output is written.  Nothing allocates, synchronises or
+ * memsets, so the calls record into a graph (after one call outside it, as the scalar
+ * transforms).  MSFNO_EINVAL for null pointers, bc < 1, plans that differ in grid, mmax or
+ * direction, are of the wrong direction, or whose degree counts are not lmax + 1 and lmax;
+ * MSFNO_EWORKSPACE for a short workspace; all before any launch.
+ * msfno_vsht_workspace_size returns 0 for a pair of plans the transforms refuse.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+int msfno_vector_legendre_table(int mmax, int lmax, int nlat, int grid, int inverse,
+                                int csphase, double* table);
+size_t msfno_vsht_workspace_size(msfno_sht_plan_t plan_d, msfno_sht_plan_t plan_q, int bc);
+int msfno_vsht_forward(msfno_sht_plan_t plan_d, msfno_sht_plan_t plan_q, const float* v,
+                       float* st, int bc, void* ws, size_t ws_bytes, void* stream);
+int msfno_vsht_inverse(msfno_sht_plan_t plan_d, msfno_sht_plan_t plan_q, const float* st,
+                       float* v, int bc, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Contractions (MSFNO/Models/sfno/contractions.py)
  * ------------------------------------------------------------------------- */
 /* compl_contract_fwd_c  (contractions.py:37-41, einsum "bin,kin->bkn"):

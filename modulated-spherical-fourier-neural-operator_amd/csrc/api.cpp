@@ -149,6 +149,76 @@ static int legendre_table(int mmax, int lmax, int nlat, int grid, int inverse, i
   return MSFNO_OK;
 }
 
+// The vector transform's tables D = dP̄_l^m/dθ and Q = m P̄_l^m / sin θ (out: (2, mmax,
+// lmax, nlat)), from the recurrence of legendre_table run one order further.  With the
+// Condon-Shortley phase in P̄ (p below) and l >= m:
+//   D_l^m = -1/2 [ sqrt((l+m)(l-m+1)) P̄_l^{m-1} - sqrt((l-m)(l+m+1)) P̄_l^{m+1} ]   (m >= 1)
+//   D_l^0 = sqrt(l(l+1)) P̄_l^1
+//   Q_l^m = -1/2 sqrt((2l+1)/(2l-1)) [ sqrt((l-m)(l-m-1)) P̄_{l-1}^{m+1}
+//                                     + sqrt((l+m)(l+m-1)) P̄_{l-1}^{m-1} ]       (m >= 1)
+// Nothing divides by sin θ: at a pole x = ±1 exactly, every P̄ of order >= 1 is an exact
+// zero, so only m = 1 survives there (through the order-0 terms) and D = Q.  Without the
+// phase both tables carry (-1)^m, as P̄ does.  inverse == 0: times w_k / (l(l+1)), the
+// l = 0 row zero.
+static int vector_legendre_table(int mmax, int lmax, int nlat, int grid, int inverse, int csphase,
+                                 double* out) {
+  std::vector<double> x, w;
+  MSFNO_TRY(quadrature(nlat, grid, x, w));
+  const int nmax = std::max(mmax + 1, lmax) + 1;  // orders <= mmax, degrees < lmax
+  std::vector<double> ca((size_t)nmax * nmax, 0.0), cb((size_t)nmax * nmax, 0.0);
+  for (int l = 2; l < nmax; ++l)
+    for (int m = 0; m < l - 1; ++m) {
+      ca[(size_t)m * nmax + l] = std::sqrt((2.0 * l - 1) / (l - m) * (2.0 * l + 1) / (l + m));
+      cb[(size_t)m * nmax + l] = std::sqrt((double)(l + m - 1) / (l - m) * (2.0 * l + 1) /
+                                           (2.0 * l - 3) * (l - m - 1) / (l + m));
+    }
+  std::vector<double> vdm((size_t)nmax * nmax);
+  const size_t plane = (size_t)mmax * lmax * nlat;
+  for (int k = 0; k < nlat; ++k) {
+    const double xk = std::cos(std::acos(x[nlat - 1 - k]));
+    std::fill(vdm.begin(), vdm.end(), 0.0);
+    auto V = [&](int m, int l) -> double& { return vdm[(size_t)m * nmax + l]; };
+    V(0, 0) = 1.0 / std::sqrt(4.0 * M_PI);
+    for (int l = 1; l < nmax; ++l) {
+      V(l - 1, l) = std::sqrt(2.0 * l + 1) * xk * V(l - 1, l - 1);
+      V(l, l) = std::sqrt((2.0 * l + 1) * (1 + xk) * (1 - xk) / 2.0 / l) * V(l - 1, l - 1);
+    }
+    for (int m = 0; m < nmax; ++m) {
+      const double* a = &ca[(size_t)m * nmax];
+      const double* b = &cb[(size_t)m * nmax];
+      double* v = &vdm[(size_t)m * nmax];
+      for (int l = m + 2; l < nmax; ++l) v[l] = xk * a[l] * v[l - 1] - b[l] * v[l - 2];
+    }
+    // p(m, l): P̄_l^m with the Condon-Shortley phase (0 for l < m)
+    auto p = [&](int m, int l) { return (m & 1) ? -V(m, l) : V(m, l); };
+    for (int m = 0; m < mmax; ++m) {
+      const double sgn = (!csphase && (m & 1)) ? -1.0 : 1.0;
+      for (int l = 0; l < lmax; ++l) {
+        double d = 0.0, q = 0.0;
+        if (l >= m && l >= 1) {
+          const double dl = l, dm = m;
+          if (m == 0) {
+            d = std::sqrt(dl * (dl + 1)) * p(1, l);
+          } else {
+            d = -0.5 * (std::sqrt((dl + dm) * (dl - dm + 1)) * p(m - 1, l) -
+                        std::sqrt((dl - dm) * (dl + dm + 1)) * p(m + 1, l));
+            q = -0.5 * std::sqrt((2 * dl + 1) / (2 * dl - 1)) *
+                (std::sqrt((dl - dm) * (dl - dm - 1)) * p(m + 1, l - 1) +
+                 std::sqrt((dl + dm) * (dl + dm - 1)) * p(m - 1, l - 1));
+          }
+          const double f = sgn * (inverse ? 1.0 : w[k] / (dl * (dl + 1)));
+          d *= f;
+          q *= f;
+        }
+        const size_t at = ((size_t)m * lmax + l) * nlat + k;
+        out[at] = d;
+        out[plane + at] = q;
+      }
+    }
+  }
+  return MSFNO_OK;
+}
+
 // ---------------------------------------------------------------------------
 // stage profiler (hipEvents on the caller's stream)
 // ---------------------------------------------------------------------------
@@ -1436,6 +1506,94 @@ int msfno_sht_inverse(msfno_sht_plan_t p, const float* in, float* x, int bc, voi
   MSFNO_TRY(transpose_inv_plan(p, Yt, Yn, 1, bc, s));
   MSFNO_TRY(launch_fft_c2r_rows(p->fft, Yn, x, nullptr, nullptr, (int64_t)bc * p->nlat, p->mmax, 0, s));
   return MSFNO_OK;
+}
+
+int msfno_vector_legendre_table(int mmax, int lmax, int nlat, int grid, int inverse, int csphase,
+                                double* table) {
+  MSFNO_REQUIRE(mmax > 0 && lmax > 0 && nlat > 0 && table, MSFNO_EINVAL, "bad table arguments");
+  return vector_legendre_table(mmax, lmax, nlat, grid, inverse, csphase, table);
+}
+
+// ---------------------------------------------------------------------------
+// Vector transforms: two scalar transforms per direction (plan_d: D moved up one
+// degree, plan_q: Q) joined by the streaming kernels of vector.hip
+// ---------------------------------------------------------------------------
+namespace {
+struct VshtBufs {
+  float2* d = nullptr;    // plan_d's spectra (2bc, lmax + 1, mmax)
+  float2* q = nullptr;    // plan_q's spectra (2bc, lmax, mmax)
+  float* grid = nullptr;  // inverse only: plan_q's fields (2bc, nlat, nlon)
+  void* sht = nullptr;    // the scalar transforms' workspace, used by one after the other
+  size_t sht_bytes = 0;
+};
+
+int vsht_pair_ok(msfno_sht_plan_t pd, msfno_sht_plan_t pq, int bc) {
+  MSFNO_REQUIRE(pd && pq, MSFNO_EINVAL, "null vector transform plan");
+  MSFNO_REQUIRE(bc >= 1, MSFNO_EINVAL, "vector transform: bc must be >= 1");
+  MSFNO_REQUIRE(pd->nlat == pq->nlat && pd->nlon == pq->nlon && pd->mmax == pq->mmax &&
+                    pd->inverse == pq->inverse,
+                MSFNO_EINVAL, "vector transform: the two plans differ in grid, mmax or direction");
+  MSFNO_REQUIRE(pd->lmax == pq->lmax + 1, MSFNO_EINVAL,
+                "vector transform: plan_d must have lmax + 1 degrees and plan_q lmax");
+  return MSFNO_OK;
+}
+
+size_t vsht_carve(Carve& cv, VshtBufs& b, msfno_sht_plan_t pd, msfno_sht_plan_t pq, int bc) {
+  const int64_t n2 = 2LL * bc;
+  b.d = cv.take<float2>(n2 * pd->lmax * pd->mmax);
+  b.q = cv.take<float2>(n2 * pq->lmax * pq->mmax);
+  if (pd->inverse) b.grid = cv.take<float>(n2 * pd->nlat * pd->nlon);
+  b.sht_bytes = std::max(msfno_sht_workspace_size(pd, (int)n2), msfno_sht_workspace_size(pq, (int)n2));
+  b.sht = cv.take<char>(b.sht_bytes);
+  return cv.off;
+}
+}  // namespace
+
+size_t msfno_vsht_workspace_size(msfno_sht_plan_t pd, msfno_sht_plan_t pq, int bc) {
+  if (vsht_pair_ok(pd, pq, bc) != MSFNO_OK || bc > INT32_MAX / 2) return 0;
+  Carve cv;
+  VshtBufs b;
+  return vsht_carve(cv, b, pd, pq, bc);
+}
+
+int msfno_vsht_forward(msfno_sht_plan_t pd, msfno_sht_plan_t pq, const float* v, float* st,
+                       int bc, void* ws, size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(v && st && ws, MSFNO_EINVAL, "msfno_vsht_forward: null pointer");
+  MSFNO_TRY(vsht_pair_ok(pd, pq, bc));
+  MSFNO_REQUIRE(bc <= INT32_MAX / 2, MSFNO_EINVAL, "vector transform: bc too large");
+  MSFNO_REQUIRE(!pd->inverse, MSFNO_EINVAL, "msfno_vsht_forward needs forward plans");
+  MSFNO_REQUIRE(pd->table_loaded && pq->table_loaded, MSFNO_EINVAL, "plan table not loaded");
+  Carve cv;
+  VshtBufs b;
+  cv.base = (char*)ws;
+  MSFNO_REQUIRE(ws_bytes >= vsht_carve(cv, b, pd, pq, bc), MSFNO_EWORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  // (bc, 2, nlat, nlon) is a batch of 2 bc scalar fields
+  MSFNO_TRY(msfno_sht_forward(pd, v, reinterpret_cast<float*>(b.d), 2 * bc, b.sht, b.sht_bytes, s));
+  MSFNO_TRY(msfno_sht_forward(pq, v, reinterpret_cast<float*>(b.q), 2 * bc, b.sht, b.sht_bytes, s));
+  return launch_vsht_combine(b.d, b.q, reinterpret_cast<float2*>(st), bc, pq->lmax, pq->mmax, s);
+}
+
+int msfno_vsht_inverse(msfno_sht_plan_t pd, msfno_sht_plan_t pq, const float* st, float* v,
+                       int bc, void* ws, size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(v && st && ws, MSFNO_EINVAL, "msfno_vsht_inverse: null pointer");
+  MSFNO_TRY(vsht_pair_ok(pd, pq, bc));
+  MSFNO_REQUIRE(bc <= INT32_MAX / 2, MSFNO_EINVAL, "vector transform: bc too large");
+  MSFNO_REQUIRE(pd->inverse, MSFNO_EINVAL, "msfno_vsht_inverse needs inverse plans");
+  MSFNO_REQUIRE(pd->table_loaded && pq->table_loaded, MSFNO_EINVAL, "plan table not loaded");
+  Carve cv;
+  VshtBufs b;
+  cv.base = (char*)ws;
+  MSFNO_REQUIRE(ws_bytes >= vsht_carve(cv, b, pd, pq, bc), MSFNO_EWORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  MSFNO_TRY(launch_vsht_pack(reinterpret_cast<const float2*>(st), b.d, b.q, bc, pq->lmax,
+                             pq->mmax, s));
+  // plan_d's fields go to v, plan_q's beside them; the add joins them in place
+  MSFNO_TRY(msfno_sht_inverse(pd, reinterpret_cast<const float*>(b.d), v, 2 * bc, b.sht,
+                              b.sht_bytes, s));
+  MSFNO_TRY(msfno_sht_inverse(pq, reinterpret_cast<const float*>(b.q), b.grid, 2 * bc, b.sht,
+                              b.sht_bytes, s));
+  return launch_vsht_add(v, b.grid, 2LL * bc * pd->nlat * pd->nlon, s);
 }
 
 int msfno_compl_contract_fwd_c(const float* a, const float* w, float* y, int B, int Ci, int Co,

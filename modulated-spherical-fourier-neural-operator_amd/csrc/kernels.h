@@ -185,6 +185,17 @@ int launch_spectrum_power(const float* coeffs, float* power, int64_t rows, int m
 // dcoeffs[r][m] = (2 e_m gpower[r]) coeffs[r][m], e_0 = 1, e_m = 2 (m >= 1)
 int launch_spectrum_power_backward(const float* coeffs, const float* gpower, float* dcoeffs,
                                    int64_t rows, int mmax, hipStream_t s);
+// ---- vector.hip: the streams between the two scalar transforms of a vector transform ------
+// A (2bc, lmax + 1, mmax), B (2bc, lmax, mmax) complex -> st (bc, 2, lmax, mmax):
+// s = A_theta[l+1] - i B_phi[l], t = A_phi[l+1] + i B_theta[l]; zeros where l < m or l = 0
+int launch_vsht_combine(const float2* A, const float2* B, float2* st, int bc, int lmax, int mmax,
+                        hipStream_t s);
+// st -> Cd (2bc, lmax + 1, mmax) = (s, t) at l + 1 under a zero row, Cq (2bc, lmax, mmax) =
+// (-i t, i s); zeros where l < m
+int launch_vsht_pack(const float2* st, float2* Cd, float2* Cq, int bc, int lmax, int mmax,
+                     hipStream_t s);
+// v[i] += q[i], i < n
+int launch_vsht_add(float* v, const float* q, int64_t n, hipStream_t s);
 // full block backward (block_bwd.cpp): per-row InstanceNorm moments and affine,
 // InstanceNorm backward (with the FiLM factor 1 + gamma s and up to two addends),
 // ComplexReLU(real) mask, complex conjugate transposes, tril <-> dense spectra, fill

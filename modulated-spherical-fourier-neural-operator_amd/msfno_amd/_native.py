@@ -96,6 +96,10 @@ SIGNATURES = [
     ("msfno_sht_workspace_size", _sz, [_vp, _i]),
     ("msfno_sht_forward", _i, [_vp, _vp, _vp, _i, _vp, _sz, _vp]),
     ("msfno_sht_inverse", _i, [_vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    ("msfno_vector_legendre_table", _i, [_i, _i, _i, _i, _i, _i, _vp]),
+    ("msfno_vsht_workspace_size", _sz, [_vp, _vp, _i]),
+    ("msfno_vsht_forward", _i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    ("msfno_vsht_inverse", _i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     ("msfno_compl_contract_fwd_c", _i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     ("msfno_compl_mul2d_fwd_c", _i, [_vp, _vp, _vp, _i, _i, _i, ctypes.c_longlong, _i, _vp]),
     ("msfno_conv1x1_workspace_size", _sz, [_i, _i, _i]),

@@ -21,6 +21,7 @@ slot, nothing synchronises); ``Rollout.verify`` drives it.
 """
 from __future__ import annotations
 
+import math
 from collections import namedtuple
 
 import torch
@@ -159,6 +160,22 @@ def mse_normalised(mse, stds):
         raise ValueError(f"stds must hold one value per channel ({mse.shape[-1]}), got "
                          f"{stds.numel()}")
     return mse / stds ** 2
+
+
+def kinetic_energy_spectrum(u, v, vsht):
+    """Kinetic energy per degree (..., lmax) of the wind ``(u, v)`` (..., nlat, nlon),
+    eastward and northward, on the unit sphere, through ``vsht``, a
+    ``harmonics.RealVectorSHT`` of the fields' grid:
+
+        KE_l = l(l+1) / (8 pi) [power(s)_l + power(t)_l]
+
+    with ``power`` of ``harmonics.power_spectrum``; its sum over l is the global mean of
+    ``|v|^2 / 2`` of the band-limited wind.  Differentiable in u and v, and bitwise
+    reproducible like the power spectrum."""
+    from .harmonics import power_spectrum, uv_to_vector
+    p = power_spectrum(vsht(uv_to_vector(u, v)))  # (..., 2, lmax)
+    l = torch.arange(p.shape[-1], device=p.device, dtype=torch.float32)
+    return (p[..., 0, :] + p[..., 1, :]) * (l * (l + 1) / (8 * math.pi))
 
 
 class Verifier(F.SlotVerifier):
