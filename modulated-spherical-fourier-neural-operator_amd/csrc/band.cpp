@@ -147,7 +147,6 @@ void carve_band(Carve& cv, BandBufs& b, const msfno_block_desc* d, const msfno_b
   const int64_t Pin = (int64_t)p->rows_in * p->nlon_in;
   const int64_t Pout = (int64_t)p->rows_out * p->nlon_out;
   const int64_t rmax = std::max(p->rows_in, p->rows_out);
-  const SpecLayout& L = p->fwd->spec;
   b.Xn = cv.take<float2>(BC * rmax * p->mmax);
   b.rs = cv.take<float2>(BC * rmax);
   b.sc0 = cv.take<float>(BC);
@@ -156,28 +155,7 @@ void carve_band(Carve& cv, BandBufs& b, const msfno_block_desc* d, const msfno_b
   b.sh1 = cv.take<float>(BC);
   b.ab1 = cv.take<float>(BC);
   std::memset(&b.fb, 0, sizeof(b.fb));
-  b.fb.Sa = cv.take<float>(R * L.ldT);
-  if (d->filter_type == MSFNO_FILTER_NONLINEAR) {
-    const int64_t Hs = d->spec_hidden;
-    b.fb.Sb = cv.take<float>(spec_hidden_floats(B, Hs, L));
-    b.fb.Sc = cv.take<float>(spec_hidden_floats(B, Hs, L));
-    b.fb.cs = cv.take<float>(2LL * B * round_up(L.Tp, 4));
-    for (int l = 0; l <= d->spectral_layers && l < 9; ++l) {
-      const int64_t ci = (l == 0) ? C : Hs;
-      const int64_t co = (l == d->spectral_layers) ? C : Hs;
-      b.fb.Wexp[l] = cv.take<float>(4 * ci * co);
-    }
-    if (d->wcache) {
-      Carve wc;
-      wc.base = static_cast<char*>(d->wcache);
-      carve_spec_ws(wc, b.fb.dw, d);
-    } else {
-      carve_spec_ws(cv, b.fb.dw, d);
-    }
-  } else {
-    b.fb.xt = cv.take<float>(std::max<int64_t>(BC * L.T * 2, 4));
-    b.fb.yt = cv.take<float>(std::max<int64_t>(BC * L.T * 2, 4));
-  }
+  carve_filter(cv, b.fb, d, p->fwd->spec, B, 4);
   b.x1 = cv.take<float>(BC * Pout);
   b.W1f = b.b1f = b.h = nullptr;
   if (mlp_fused(d, Pout)) {

@@ -1,6 +1,8 @@
-// Internal block-orchestration helpers shared by api.cpp (single-GPU block)
-// and band.cpp (latitude-band sharded block).  Not part of the C-ABI.
+// Internal helpers shared by the host units: plan.cpp (plans, Legendre launches),
+// block_fwd.cpp (single-GPU block), block_bwd.cpp, band.cpp (latitude-band sharded block),
+// mlp.cpp, profile.cpp.  Not part of the C-ABI.
 #pragma once
+#include <functional>
 #include <memory>
 #include "kernels.h"
 
@@ -75,6 +77,10 @@ struct BlockBufs {
 
 void carve_block(Carve& cv, BlockBufs& b, const msfno_block_desc* d, const msfno_sht_plan_s* f,
                  const msfno_sht_plan_s* g, int B, bool with_norms);
+// the spectral filter's buffers in layout L (Sa ... xt / yt, the spectral weight images
+// in the workspace or in d->wcache); xt / yt hold at least tril_floor floats
+void carve_filter(Carve& cv, BlockBufs& b, const msfno_block_desc* d, const SpecLayout& L, int B,
+                  int64_t tril_floor);
 int check_pair(const msfno_block_desc* d, const msfno_sht_plan_s* f, const msfno_sht_plan_s* g);
 int ensure_desc(msfno_sht_plan_s* p, int R, int other_ld, int64_t ldT, hipStream_t s = nullptr);
 int transpose_fwd_plan(const msfno_sht_plan_s* p, const float2* Xn, float* Xt, int B, int C,
@@ -83,12 +89,28 @@ int transpose_inv_plan(const msfno_sht_plan_s* p, const float* Yt, float2* Yn, i
                        hipStream_t s);
 int legendre_fwd(msfno_sht_plan_s* f, const float* Xt, float* S, int R, hipStream_t s);
 int legendre_inv(msfno_sht_plan_s* g, const float* S, float* Yt, int R, hipStream_t s);
-// spectral filter on S (f->spec layout) in b.Sa (in place)
+bool leg_x3_enabled();
+bool x3f_env();
 bool x3f_usable(msfno_sht_plan_s* f);
 int legendre_fwd_x3f(msfno_sht_plan_s* f, const unsigned short* Xp, const float* isr, float* S,
                      int R, hipStream_t s);
+// spectral filter on S (f->spec layout) in b.Sa (in place)
 int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
                const BlockBufs& b, int B, hipStream_t s);
+// x -> (FFT, norm0 folded) -> Legendre -> filter -> inverse Legendre -> Yn
+// xplanes: the forward FFT also writes x as bf16x3 planes; after_fft runs once the
+// forward FFT is enqueued (the block forks its inner-skip GEMM there)
+int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
+                 const BlockBufs& b, const float* x, int B, bool norm0, hipStream_t s,
+                 const C2RPlanes* xplanes = nullptr,
+                 const std::function<int()>& after_fft = std::function<int()>(),
+                 const std::function<int()>& after_norm0 = std::function<int()>(),
+                 const std::function<int()>& after_leg = std::function<int()>(),
+                 const std::function<int()>& before_inv = std::function<int()>());
+// Yt -> spatial rows; out = act(addsrc + irfft)
+int run_inverse_fft(msfno_sht_plan_s* g, const BlockBufs& b, int B, int C, float* out,
+                    const float* addsrc, float2* rowstats, int act, hipStream_t s,
+                    unsigned short* planes = nullptr);
 void set_table_offsets(msfno_sht_plan_s* p, int sym);
 // channel MLP with norm1/FiLM folded into (W1f, b1f): out = W2·GELU(W1f·x1 + b1f) + b2 (+resid)
 int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const float* x1,

@@ -8,12 +8,10 @@
 #include <map>
 #include <vector>
 
-#include "../../include/msfno.h"
+#include "error.h"
 #include "switches.h"
 
 namespace msfno {
-
-void set_error(const std::string& msg);
 
 struct Status {
   int code = MSFNO_OK;
@@ -28,20 +26,6 @@ struct Status {
                          " in " #expr);                                             \
       return MSFNO_EHIP;                                                            \
     }                                                                               \
-  } while (0)
-
-#define MSFNO_REQUIRE(cond, code, msg)          \
-  do {                                          \
-    if (!(cond)) {                              \
-      ::msfno::set_error(msg);                  \
-      return (code);                            \
-    }                                           \
-  } while (0)
-
-#define MSFNO_TRY(expr)              \
-  do {                               \
-    int _rc = (expr);                \
-    if (_rc != MSFNO_OK) return _rc; \
   } while (0)
 
 inline int launch_check(const char* what) {

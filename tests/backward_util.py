@@ -30,6 +30,22 @@ def _compare(tag, got, want, rel=1e-4, scale=0.0):
     assert err < tol, (tag, err, tol)
 
 
+def _film_oracle_grads(meta, params, x, gamma0, beta0, scale, dout):
+    """(dL/dgamma, dL/dbeta) of L = (block(x) * dout).sum() by torch autograd through the
+    fp64 oracle block of the fixture (meta, params)."""
+    from golden_util import wiring_cfg
+    inner, outer, has_mlp = wiring_cfg(meta)
+    cfg = sfno_ref.BlockCfg(filter_type=meta["filter"], inner_skip=inner, outer_skip=outer,
+                            has_mlp=has_mlp)
+    pd = {k: (v.double() if v.is_floating_point() else v) for k, v in params.items()}
+    sht, isht = _oracle_transforms(meta)
+    gd = gamma0.double().requires_grad_()
+    bd = beta0.double().requires_grad_()
+    yd = sfno_ref.block_forward(pd, x.double(), sht, isht, cfg, gd, bd, scale)
+    (yd * dout.double()).sum().backward()
+    return gd.grad, bd.grad
+
+
 def _compare_params(tag, named, want_of):
     """Every (name, parameter) of `named` against want_of(name); a bias is held to its
     weight's gradient scale as well (_compare)."""

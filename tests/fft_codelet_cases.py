@@ -282,7 +282,7 @@ assert len(set(BLOCK_IDS)) == len(BLOCK_IDS)
 
 
 def block_planes(c, dma=True):
-    """api.cpp x1_planes: the inverse FFT writes the MLP's input as planes when the block has
+    """block_fwd.cpp x1_planes: the inverse FFT writes the MLP's input as planes when the block has
     an (unfused: C != 256) MLP, the pixel count is a multiple of 8 and
     fft_c2r_planes_supported; global_conv (cases without MLP) never asks for planes."""
     return bool(c.mlp and dma and (c.nlat * c.nlon) % 8 == 0 and is_dma(c.nlon, c.mmax)

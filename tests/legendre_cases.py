@@ -2,7 +2,7 @@
 test_legendre_cases_host.py and test_gpu_legendre_shapes.py.
 
 The Legendre stage is a family of kernels and template bodies picked by shape
-(csrc/api.cpp ensure_desc3, x3f_usable; csrc/legendre_x3.hip):
+(csrc/plan.cpp ensure_desc3, x3f_usable; csrc/legendre_x3.hip):
 
   legendre_x3_kernel   tiled, X3D_BM rows x X3D_BN columns, k-tiles of X3D_BK: the forward
                        transform of a stand-alone RealSHT, and every fallback;

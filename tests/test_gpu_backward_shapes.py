@@ -24,6 +24,7 @@ from backward_util import _compare, _compare_params, _masked_oracle, _oracle_tra
 from block_util import make_block
 from golden_util import param_recipe, recipe_normal, wiring_cfg
 from oracle import sfno_ref
+from workspace_guard import guard_intact, guarded
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -151,10 +152,7 @@ def test_mlp_backward_params_abi_workspace_holds_anything_and_is_not_overrun():
     L = N.lib()
     nbytes = L.msfno_mlp_backward_params_workspace_size(d, B, P)
     assert nbytes > 0
-    guard = 4096
-    buf = torch.empty(nbytes + guard, dtype=torch.uint8, device=DEV)
-    buf[:nbytes] = 0xFF
-    buf[nbytes:] = 0x5A
+    buf = guarded(nbytes, 0xFF, DEV)
     x, dy = t["x"].to(DEV).contiguous(), t["dy"].to(DEV).contiguous()
     outs = {"dx": (B, Cin, 1, P), "dfc1_w": (Hid, Cin, 1, 1), "dfc1_b": (Hid,),
             "dfc2_w": (Cout, Hid, 1, 1), "dfc2_b": (Cout,)}
@@ -171,7 +169,7 @@ def test_mlp_backward_params_abi_workspace_holds_anything_and_is_not_overrun():
         return rc
 
     assert call(nbytes) == N.MSFNO_OK, L.msfno_last_error()
-    assert (buf[nbytes:] == 0x5A).all(), "the call wrote past the workspace it asked for"
+    guard_intact(buf, nbytes)
     got = dict(outs, dx2=None)
     _mlp_compare("abi", got, want)
     assert torch.equal(x.cpu(), t["x"]) and torch.equal(dy.cpu(), t["dy"])
@@ -181,7 +179,7 @@ def test_mlp_backward_params_abi_workspace_holds_anything_and_is_not_overrun():
     assert call(nbytes - 1) == N.MSFNO_EWORKSPACE
     for k, o in outs.items():
         assert torch.isnan(o).all(), f"{k} written by a refused call"
-    assert (buf[nbytes:] == 0x5A).all()
+    guard_intact(buf, nbytes)
     del keep
 
 
@@ -277,7 +275,7 @@ def _recipe_params(blk, meta):
     return params
 
 
-def _guarded_workspace(blk, x, B, guard=4096):
+def _guarded_workspace(blk, x, B):
     """(ws, nbytes): msfno_block_backward_params_workspace_size bytes of 0xFF, then a guard."""
     from msfno_amd import _native as N
     fwd, inv = blk._transforms()
@@ -288,10 +286,7 @@ def _guarded_workspace(blk, x, B, guard=4096):
                                                                 fa.handle, ga.handle, B)
     del keep
     assert nbytes > 0
-    ws = torch.empty(nbytes + guard, dtype=torch.uint8, device=x.device)
-    ws[:nbytes] = 0xFF
-    ws[nbytes:] = 0x5A
-    return ws, nbytes
+    return guarded(nbytes, 0xFF, x.device), nbytes
 
 
 def _block_case(name, guard_ws=False):
@@ -328,7 +323,7 @@ def _block_case(name, guard_ws=False):
     torch.cuda.synchronize()
     if guard_ws:
         assert len(calls) == 1
-        assert (ws[nbytes:] == 0x5A).all(), "the backward wrote past the workspace it asked for"
+        guard_intact(ws, nbytes)
     inner, outer, has_mlp = wiring_cfg(meta)
     cfg = sfno_ref.BlockCfg(filter_type=meta["filter"], inner_skip=inner, outer_skip=outer,
                             has_mlp=has_mlp)

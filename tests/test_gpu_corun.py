@@ -34,6 +34,13 @@ def _conv(w, b, x, stream=None):
     return out, ws
 
 
+def _conv_error(y, w, b, x):
+    """max |y - fp64| / sum_i |w| |x|, the scale of the products that meet in each output"""
+    ref = torch.einsum("oi,bip->bop", w.double(), x.double()) + b.double()[None, :, None]
+    mag = torch.einsum("oi,bip->bop", w.double().abs(), x.double().abs())
+    return ((y.double() - ref).abs() / (mag + 1e-30)).max().item()
+
+
 @pytest.mark.parametrize("B,Cin,Cout,P", [(2, 256, 256, 120 * 240), (1, 64, 32, 4000),
                                           (3, 256, 256, 1000), (3, 256, 256, 50000),
                                           (1, 256, 256, 1038)])
@@ -50,10 +57,7 @@ def test_conv1x1_matches_fp64(B, Cin, Cout, P):
     b = torch.randn(Cout, generator=g, device=DEV)
     y, _ = _conv(w, b, x)
     torch.cuda.synchronize()
-    ref = torch.einsum("oi,bip->bop", w.double(), x.double()) + b.double()[None, :, None]
-    # scale of the products that meet in each output: sum_i |w| |x|
-    mag = torch.einsum("oi,bip->bop", w.double().abs(), x.double().abs())
-    err = ((y.double() - ref).abs() / (mag + 1e-30)).max().item()
+    err = _conv_error(y, w, b, x)
     print(f"conv1x1 B={B} {Cin}->{Cout} P={P}: max |err| / sum|w x| = {err:.3e}")
     assert err < 2e-6
 

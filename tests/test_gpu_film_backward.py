@@ -15,8 +15,8 @@ import os
 import pytest
 import torch
 
-from backward_util import (_compare, _compare_params, _masked_oracle,  # noqa: F401
-                           _oracle_transforms, _tap_blocks)
+from backward_util import (_compare, _compare_params, _film_oracle_grads,  # noqa: F401
+                           _masked_oracle, _oracle_transforms, _tap_blocks)
 from block_util import make_block
 from golden_util import golden_files, load, wiring_cfg
 from oracle import sfno_ref
@@ -44,16 +44,8 @@ def test_block_film_grads_match_oracle_autograd(path):
     dout = torch.randn(y.shape, generator=g)
     (y * dout.to(DEV)).sum().backward()
     # oracle: torch autograd in fp64
-    inner, outer, has_mlp = wiring_cfg(meta)
-    cfg = sfno_ref.BlockCfg(filter_type=meta["filter"], inner_skip=inner, outer_skip=outer,
-                            has_mlp=has_mlp)
-    pd = {k: (v.double() if v.is_floating_point() else v) for k, v in params.items()}
-    sht, isht = _oracle_transforms(meta)
-    gd = gamma0.double().requires_grad_()
-    bd = beta0.double().requires_grad_()
-    yd = sfno_ref.block_forward(pd, x.double(), sht, isht, cfg, gd, bd, scale)
-    (yd * dout.double()).sum().backward()
-    for got, want in ((gamma.grad, gd.grad), (beta.grad, bd.grad)):
+    wg, wb = _film_oracle_grads(meta, params, x, gamma0, beta0, scale, dout)
+    for got, want in ((gamma.grad, wg), (beta.grad, wb)):
         got = got.cpu().double()
         assert got.shape == want.shape
         tol = 1e-4 * max(want.abs().max().item(), 1e-6)

@@ -2,7 +2,7 @@
 the cases, their fp64 references and the measures; test_legendre_cases_host.py the
 conditions that give the bars their meaning).
 
-Which kernel a case reaches follows csrc/api.cpp:
+Which kernel a case reaches follows csrc/plan.cpp:
 
 * stand-alone RealSHT (msfno_sht_forward -> legendre_fwd): always legendre_x3_kernel, the
   tiled one, 128 rows x 64 columns, ceil(K / 32) k-tiles with K = Ke (even problems) or Ko
@@ -59,10 +59,10 @@ if __name__ == "__main__":             # the MSFNO_X3F_NS=2 child: no conftest s
         sys.path.insert(0, _p)
 
 import legendre_cases as L  # noqa: E402
+from workspace_guard import guard_intact as _guard_intact, guarded as _guarded  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-GUARD = 4096
 
 
 # ---- stand-alone transforms through the C ABI ---------------------------------------
@@ -77,18 +77,6 @@ def _module(cls, c):
         else:
             mod.pct = L.table(c, True).float()
     return mod.to(DEV)
-
-
-def _guarded(nbytes, fill):
-    ws = torch.empty(nbytes + GUARD, dtype=torch.uint8, device=DEV)
-    ws[:nbytes] = fill
-    ws[nbytes:] = 0x5A
-    return ws
-
-
-def _guard_intact(ws, nbytes):
-    torch.cuda.synchronize()
-    assert (ws[nbytes:] == 0x5A).all(), "the call wrote past the workspace it asked for"
 
 
 def _sht(mod, arg, fill=0xFF):

@@ -49,6 +49,25 @@ def _case(Cin, Cin2, Hid, Cout, P, B, addend, bias, seed):
     return ((got - y64).abs() / scale).max().item(), (got - y64).abs().max().item()
 
 
+def _reference(m, x, x2, add):
+    """(y64, scale) of the CPU module m on x (B, Cin, 1, P), x2 and add (either may be
+    None): the fp64 MLP and the magnitude of the products that meet in each output."""
+    sd = {k: v.double() for k, v in m.fwd.state_dict().items()}
+    W1, b1 = sd["0.weight"][:, :, 0, 0], sd["0.bias"]
+    W2 = sd["2.weight"][:, :, 0, 0]
+    b2 = sd["2.bias"] if "2.bias" in sd else torch.zeros(W2.shape[0], dtype=torch.float64)
+    xd = x.double()[:, :, 0, :]
+    if x2 is not None:
+        xd = torch.cat([xd, x2.double()[:, :, 0, :]], 1)
+    h = _gelu64(torch.einsum("oi,bip->bop", W1, xd) + b1[None, :, None])
+    y64 = torch.einsum("oi,bip->bop", W2, h) + b2[None, :, None]
+    scale = torch.einsum("oi,bip->bop", W2.abs(), h.abs()) + b2.abs()[None, :, None]
+    if add is not None:
+        y64 = y64 + add.double()[:, :, 0, :]
+        scale = scale + add.double().abs()[:, :, 0, :]
+    return y64, scale
+
+
 def _run(Cin, Cin2, Hid, Cout, P, B, addend, bias, seed):
     from msfno_amd.sfno import MLP
     torch.manual_seed(seed)
@@ -67,19 +86,7 @@ def _run(Cin, Cin2, Hid, Cout, P, B, addend, bias, seed):
         add = torch.randn(1, Cout, 1, P)
     elif addend == "batched":
         add = torch.randn(B, Cout, 1, P)
-    sd = {k: v.double() for k, v in m.fwd.state_dict().items()}
-    W1, b1 = sd["0.weight"][:, :, 0, 0], sd["0.bias"]
-    W2 = sd["2.weight"][:, :, 0, 0]
-    b2 = sd["2.bias"] if bias else torch.zeros(Cout, dtype=torch.float64)
-    xd = x.double()[:, :, 0, :]
-    if Cin2:
-        xd = torch.cat([xd, x2.double()[:, :, 0, :]], 1)
-    h = _gelu64(torch.einsum("oi,bip->bop", W1, xd) + b1[None, :, None])
-    y64 = torch.einsum("oi,bip->bop", W2, h) + b2[None, :, None]
-    scale = torch.einsum("oi,bip->bop", W2.abs(), h.abs()) + b2.abs()[None, :, None]
-    if add is not None:
-        y64 = y64 + add.double()[:, :, 0, :]
-        scale = scale + add.double().abs()[:, :, 0, :]
+    y64, scale = _reference(m, x, x2, add)
     with torch.no_grad():
         got = m.to(DEV).native_forward(
             x.to(DEV), x2=None if x2 is None else x2.to(DEV),

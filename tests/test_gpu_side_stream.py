@@ -1,4 +1,4 @@
-"""The inner skip on its side stream (api.cpp: forked after the norm0 statistics, joined
+"""The inner skip on its side stream (block_fwd.cpp: forked after the norm0 statistics, joined
 before the inverse FFT) changes nothing but the schedule: at config 2's full size
 (721x1440, C=256, lmax 360) the block output with the side stream on must equal the
 serial one bit for bit, for both filters and at batch 1 and 2.  The skip kernel
