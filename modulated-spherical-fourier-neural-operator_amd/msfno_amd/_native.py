@@ -270,6 +270,30 @@ def require_device_f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def f32(t, keep=None):
+    """``t`` as the C ABI reads a weight: detached, fp32, contiguous (``t``'s own memory
+    when it already is).  None passes through.  The result is appended to ``keep``, the
+    list that holds a call's copies alive until the call has been issued."""
+    if t is None:
+        return None
+    t = t.detach().float().contiguous()
+    if keep is not None:
+        keep.append(t)
+    return t
+
+
+def per_channel_f32(t, B, C):
+    """A per-(batch, channel) vector (FiLM gamma / beta, a deferred affine) as (B, C) fp32
+    contiguous; None passes through."""
+    return None if t is None else f32(t).reshape(B, C)
+
+
+def tensor_key(t):
+    """Changes when ``t`` is replaced, written in place, cast or moved: what a plan or a
+    prepared copy built from ``t`` is cached under."""
+    return (t.data_ptr(), t._version, t.dtype, str(t.device))
+
+
 class SHTPlan:
     """Owns one msfno_sht_plan_t (device tables + FFT twiddles)."""
 

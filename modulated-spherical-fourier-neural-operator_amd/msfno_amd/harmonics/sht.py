@@ -101,7 +101,7 @@ class _SHTBase(nn.Module):
         if plan is None:
             plan = N.SHTPlan(self.nlat, self.nlon, self.lmax, self.mmax, self._inverse, idx)
             self._plans[idx] = plan
-        key = (table.data_ptr(), table._version, table.dtype, str(table.device))
+        key = N.tensor_key(table)
         if key != plan.key:  # (re)load only when the buffer tensor changed
             t = table
             if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
@@ -119,7 +119,7 @@ class _SHTBase(nn.Module):
         if plan is None:
             plan = N.SHTPlan(self.nlat, self.nlon, self.lmax, self.mmax, not self._inverse, idx)
             self._adj_plans[idx] = plan
-        key = (table.data_ptr(), table._version, table.dtype, str(table.device))
+        key = N.tensor_key(table)
         if key != plan.key:
             plan.load(adjoint_table(table, self.nlon, self._inverse).to(device).contiguous(),
                       key)

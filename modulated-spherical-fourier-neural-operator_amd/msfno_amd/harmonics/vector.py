@@ -70,7 +70,7 @@ class _VectorSHTBase(_SHTBase):
         pair = store.get(idx)
         if pair is None:
             pair = store[idx] = _PlanPair(self, inverse, idx)
-        key = (table.data_ptr(), table._version, table.dtype, str(table.device))
+        key = N.tensor_key(table)
         if key != pair.key:  # (re)load only when the buffer tensor changed
             if adjoint:
                 t = torch.stack([adjoint_table(table[i], self.nlon, self._inverse)

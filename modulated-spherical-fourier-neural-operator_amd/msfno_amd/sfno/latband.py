@@ -438,8 +438,7 @@ class LatBandBlock:
 
     def _tables(self):
         fwd, inv = self.block._transforms()
-        key = tuple((t.data_ptr(), t._version, t.dtype, str(t.device))
-                    for t in (fwd.weights, inv.pct))
+        key = (N.tensor_key(fwd.weights), N.tensor_key(inv.pct))
         if key == self.plan.key:  # (re)load only when a table tensor changed
             return
         tabs = []
@@ -452,12 +451,12 @@ class LatBandBlock:
     def _linear_weight(self, w):
         """This rank's slice w[:, :, modes, :] of the per-mode weight (cached until
         the parameter changes); the whole weight when the rank owns every mode."""
-        key = (w.data_ptr(), w._version, w.dtype, str(w.device))
+        key = N.tensor_key(w)
         if self._lin is not None and self._lin[0] == key:
             return self._lin[1]
         modes = self.plan.linear_modes()
         # the contraction reads fp32 (C, C, T, 2) contiguous, as _fill_desc passes it
-        wf = w.detach().float().contiguous()
+        wf = N.f32(w)
         if len(modes) == w.shape[2]:
             local = wf
         else:
@@ -502,9 +501,7 @@ class LatBandBlock:
             wl = self._linear_weight(self.block.filter_layer.filter.w)
             d.lin_w = wl.data_ptr()
             keep.append(wl)
-        if gamma is not None:
-            gamma = gamma.detach().float().reshape(B, C).contiguous()
-            beta = beta.detach().float().reshape(B, C).contiguous()
+        gamma, beta = N.per_channel_f32(gamma, B, C), N.per_channel_f32(beta, B, C)
         L = N.lib()
         wkey = self.block.wcache_attach(d, keep, x.device)  # prepared-weight images
         bufs = self._buffers(B, C, slot)

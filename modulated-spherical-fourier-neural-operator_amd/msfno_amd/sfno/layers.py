@@ -113,6 +113,58 @@ class WeightCache:
         self._wcache_key = key
 
 
+class BlockCall:
+    """One block-shaped native call of ``mod`` (a block or an S2 filter) on ``x``.
+
+    Construction is the front half every such entry point shares: x as fp32 on its
+    device, its shape checked against the transforms, the two transform plans (and the two
+    adjoint ones for a backward), the descriptor and the list that keeps its fp32 copies
+    alive.  ``run`` is the back half.  The method named after a C entry point writes only
+    that entry point's own pointer list, between ``d, *plans`` and ``B, *tail``."""
+
+    def __init__(self, mod, x, what="block input", adjoint=False):
+        self.mod, self.dtype = mod, x.dtype
+        self.x = x = N.require_device_f32(x, what)
+        self.device = x.device
+        self.B, self.C, H, W = x.shape
+        self.fwd, self.inv = fwd, inv = mod._transforms()
+        assert H == fwd.nlat and W == fwd.nlon
+        plans = (fwd._plan(x.device), inv._plan(x.device))
+        if adjoint:
+            plans += mod._adjoint_plans(x.device)
+        self.plans = tuple(p.handle for p in plans)
+        self.d, self.keep = mod.native_desc(self.C)
+
+    def empty(self, *shape):
+        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+
+    def out(self):
+        """The (B, C, nlat, nlon) result on the inverse transform's grid."""
+        return self.empty(self.B, self.C, self.inv.nlat, self.inv.nlon)
+
+    def run(self, size_fn, entry, what, cache=False, ws=None):
+        """Issue the call: with ``cache`` the module's prepared-weight cache attached before
+        and committed after; the workspace sized by the entry point's own ``size_fn`` and
+        allocated here, or the caller's ``ws`` checked against that size (it stays in
+        ``self.ws``); ``entry(ws_ptr, ws_bytes, stream)`` makes the C call."""
+        wkey = self.mod.wcache_attach(self.d, self.keep, self.device) if cache else None
+        nbytes = size_fn(self.d, *self.plans, self.B)
+        if ws is None:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        elif (ws.dtype != torch.uint8 or ws.device != self.device or ws.dim() != 1
+              or not ws.is_contiguous() or ws.numel() < nbytes):
+            raise ValueError(f"{what}: ws must be {nbytes} contiguous uint8 on {self.device}")
+        self.ws = ws
+        N.check(entry(ws.data_ptr(), nbytes, N.stream_of(self.device)), what)
+        if cache:
+            self.mod.wcache_commit(wkey)
+
+
+def block_workspace_size(d, pf, pi, B):
+    """The workspace of every forward-shaped entry point: msfno_block_forward, its
+    deferred form, msfno_block_global_conv and msfno_filter_forward."""
+    return N.lib().msfno_block_workspace_size(d, pf, pi, B)
+
 
 class DropPath(nn.Module):
     """Stochastic depth; identity at inference (the only mode of the fused path)."""
@@ -151,22 +203,21 @@ class MLP(WeightCache, nn.Module):
         else:
             self.fwd = nn.Sequential(fc1, act, fc2)
 
+    def convs(self):
+        """(fc1, fc2): the two nn.Conv2d entries of ``fwd``, with or without the dropout
+        modules between and behind them."""
+        fc1, fc2 = (m for m in self.fwd if isinstance(m, nn.Conv2d))
+        return fc1, fc2
+
     def native_desc(self, cin2=0):
-        fc1, act, fc2 = self.fwd[0], self.fwd[1], self.fwd[-1]
+        (fc1, fc2), act = self.convs(), self.fwd[1]
         if not (isinstance(act, nn.GELU) and getattr(act, "approximate", "none") == "none"):
             raise NotImplementedError("the native MLP fuses GELU(approximate='none') only")
         if self.training and len(self.fwd) > 3:
             raise NotImplementedError("MLP dropout in training mode is not fused")
         keep = []
-
-        def f32(t):
-            t = t.detach().float().contiguous()
-            keep.append(t)
-            return t
-
-        w1, w2 = f32(fc1.weight), f32(fc2.weight)
-        b1 = f32(fc1.bias)
-        b2 = f32(fc2.bias) if fc2.bias is not None else None
+        w1, w2 = N.f32(fc1.weight, keep), N.f32(fc2.weight, keep)
+        b1, b2 = N.f32(fc1.bias, keep), N.f32(fc2.bias, keep)
         d = N.MlpDesc()
         d.Cin = w1.shape[1] - cin2
         d.Cin2 = cin2
@@ -178,11 +229,9 @@ class MLP(WeightCache, nn.Module):
     def _wcache_bytes(self, d):
         return N.lib().msfno_mlp_wcache_size(d)
 
-    @N.on_input_device
-    def native_forward(self, x, x2=None, addend=None):
-        """out = fc2(GELU(fc1(cat(x, x2)))) (+ addend, broadcast over the batch when its
-        leading dimension is 1) in two MFMA GEMMs (msfno_mlp_forward); the channel
-        concatenation is consumed in place (sfnonet.py:680-686)."""
+    def _forward(self, entry, affine, what, x, x2, addend):
+        """The body of both forwards: ``entry`` is msfno_mlp_forward (``affine`` empty) or
+        msfno_mlp_forward_affine (``affine`` its two extra pointers, after x)."""
         dtype = x.dtype
         x = N.require_device_f32(x, "MLP input")
         B, Cin, H, W = x.shape
@@ -199,63 +248,40 @@ class MLP(WeightCache, nn.Module):
             addend = N.require_device_f32(addend, "MLP addend")
             assert addend.shape[1:] == (d.Cout, H, W)
             bstride = 0 if addend.shape[0] == 1 else d.Cout * H * W
-        L = N.lib()
         P = H * W
         wkey = self.wcache_attach(d, keep, x.device)
-        nbytes = L.msfno_mlp_workspace_size(d, B, P)
+        nbytes = N.lib().msfno_mlp_workspace_size(d, B, P)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty(B, d.Cout, H, W, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_mlp_forward(d, x.data_ptr(), N.ptr(x2), N.ptr(addend), bstride,
-                                    out.data_ptr(), B, P, ws.data_ptr(), nbytes,
-                                    N.stream_of(x.device)), "MLP.forward")
+        N.check(entry(d, x.data_ptr(), *affine, N.ptr(x2), N.ptr(addend), bstride,
+                      out.data_ptr(), B, P, ws.data_ptr(), nbytes, N.stream_of(x.device)), what)
         self.wcache_commit(wkey)
-        del keep
         return out.to(dtype)
+
+    @N.on_input_device
+    def native_forward(self, x, x2=None, addend=None):
+        """out = fc2(GELU(fc1(cat(x, x2)))) (+ addend, broadcast over the batch when its
+        leading dimension is 1) in two MFMA GEMMs (msfno_mlp_forward); the channel
+        concatenation is consumed in place (sfnonet.py:680-686)."""
+        return self._forward(N.lib().msfno_mlp_forward, (), "MLP.forward", x, x2, addend)
 
     @N.on_input_device
     def native_forward_affine(self, x, x_scale, x_shift, x2=None, addend=None):
         """native_forward of (x_scale * x + x_shift) per (batch, channel) — the deferred
         output affine of the block that produced x (msfno_mlp_forward_affine; fused widths
         only)."""
-        dtype = x.dtype
-        x = N.require_device_f32(x, "MLP input")
-        B, Cin, H, W = x.shape
-        xa = x_scale.detach().float().reshape(B, Cin).contiguous()
-        xt = x_shift.detach().float().reshape(B, Cin).contiguous()
-        cin2 = 0
-        if x2 is not None:
-            x2 = N.require_device_f32(x2, "MLP second input")
-            assert x2.shape[0] == B and x2.shape[2:] == x.shape[2:]
-            cin2 = x2.shape[1]
-        d, keep = self.native_desc(cin2)
-        if d.Cin != Cin:
-            raise ValueError(f"MLP expects {d.Cin} (+{cin2}) input channels, got {Cin}")
-        bstride = 0
-        if addend is not None:
-            addend = N.require_device_f32(addend, "MLP addend")
-            assert addend.shape[1:] == (d.Cout, H, W)
-            bstride = 0 if addend.shape[0] == 1 else d.Cout * H * W
-        L = N.lib()
-        P = H * W
-        wkey = self.wcache_attach(d, keep, x.device)
-        nbytes = L.msfno_mlp_workspace_size(d, B, P)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(B, d.Cout, H, W, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_mlp_forward_affine(d, x.data_ptr(), xa.data_ptr(), xt.data_ptr(),
-                                           N.ptr(x2), N.ptr(addend), bstride, out.data_ptr(), B,
-                                           P, ws.data_ptr(), nbytes, N.stream_of(x.device)),
-                "MLP.forward_affine")
-        self.wcache_commit(wkey)
-        del keep
-        return out.to(dtype)
+        B, Cin = x.shape[:2]
+        xa, xt = N.per_channel_f32(x_scale, B, Cin), N.per_channel_f32(x_shift, B, Cin)
+        return self._forward(N.lib().msfno_mlp_forward_affine, (xa.data_ptr(), xt.data_ptr()),
+                             "MLP.forward_affine", x, x2, addend)
 
     @N.on_input_device
     def native_backward_input(self, x, dy, x2=None, need_dx=True, params=(), need_dx2=False):
-        """dL/dx of fc2(GELU(fc1(cat(x, x2)))) (msfno_mlp_backward_params): the decoder's
-        backward in FiLM fine-tuning, plus the gradients of ``params`` (a subset of fc1 /
-        fc2 weight and bias: the decoder trains under --retrain-film, MSFNO/Models/sfno/
-        model.py:922-923), and dL/dx2 when need_dx2.  Returns dx, or (dx, [dL/dp ...])
-        when params are given, with dx2 appended when asked for."""
+        """(dx, [dL/dp ...], dx2) of fc2(GELU(fc1(cat(x, x2)))) (msfno_mlp_backward_params):
+        the decoder's backward in FiLM fine-tuning, plus the gradients of ``params`` (a
+        subset of fc1 / fc2 weight and bias: the decoder trains under --retrain-film,
+        MSFNO/Models/sfno/model.py:922-923).  dx is None unless need_dx, dx2 unless
+        need_dx2; the list is empty without ``params``."""
         x = N.require_device_f32(x, "MLP input")
         dy = N.require_device_f32(dy, "MLP output gradient")
         B, Cin, H, W = x.shape
@@ -266,7 +292,7 @@ class MLP(WeightCache, nn.Module):
         d, keep = self.native_desc(cin2)
         L = N.lib()
         P = H * W
-        fc1, fc2 = self.fwd[0], self.fwd[-1]
+        fc1, fc2 = self.convs()
         slots = {id(fc1.weight): 0, id(fc2.weight): 2}
         if fc1.bias is not None:
             slots[id(fc1.bias)] = 1
@@ -288,10 +314,7 @@ class MLP(WeightCache, nn.Module):
                                             N.ptr(dx2), *[N.ptr(t) for t in outs], B, P,
                                             ws.data_ptr(), nbytes, N.stream_of(x.device)),
                 "MLP.backward")
-        del keep
-        if need_dx2:
-            return dx, pgs, dx2
-        return (dx, pgs) if params else dx
+        return dx, pgs, dx2
 
     def forward(self, x):
         if torch.is_grad_enabled():
@@ -322,14 +345,10 @@ class _MLPFn(torch.autograd.Function):
         need2 = bool(ctx.needs_input_grad[1])  # the decoder's big skip (the network input)
         dx, dx2, pgs = None, None, []
         if ctx.needs_input_grad[0] or wanted or need2:
-            res = ctx.mlp.native_backward_input(x, dy, x2=x2, need_dx=ctx.needs_input_grad[0],
-                                                params=wanted, need_dx2=need2)
-            if need2:
-                dx, pgs, dx2 = res
-                dx2 = dx2.to(x2.dtype)
-            else:
-                dx, pgs = res if wanted else (res, [])
+            dx, pgs, dx2 = ctx.mlp.native_backward_input(
+                x, dy, x2=x2, need_dx=ctx.needs_input_grad[0], params=wanted, need_dx2=need2)
             dx = dx.to(x.dtype) if dx is not None else None
+            dx2 = dx2.to(x2.dtype) if dx2 is not None else None
         dadd = None
         if ctx.needs_input_grad[2]:  # the encoder's pos_embed, broadcast over the batch
             dadd = dy.sum(0, keepdim=True) if ctx.addend_shape[0] == 1 else dy
@@ -362,23 +381,12 @@ class _S2FilterBase(nn.Module):
 
     @N.on_input_device
     def forward(self, x):
-        dtype = x.dtype
-        x = N.require_device_f32(x, "filter input")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        assert H == fwd.nlat and W == fwd.nlon
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        d, keep = self.native_desc(C)
-        L = N.lib()
-        nbytes = L.msfno_block_workspace_size(d, pf.handle, pi.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        y = torch.empty(B, C, inv.nlat, inv.nlon, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_filter_forward(d, pf.handle, pi.handle, x.data_ptr(), y.data_ptr(), B,
-                                       ws.data_ptr(), nbytes, N.stream_of(x.device)),
-                type(self).__name__ + ".forward")
-        del keep
-        return y.to(dtype)
+        c = BlockCall(self, x, "filter input")
+        y = c.out()
+        c.run(block_workspace_size, lambda *tail: N.lib().msfno_filter_forward(
+            c.d, *c.plans, c.x.data_ptr(), y.data_ptr(), c.B, *tail),
+            type(self).__name__ + ".forward")
+        return y.to(c.dtype)
 
 
 class SpectralConvS2(_S2FilterBase):
@@ -418,12 +426,8 @@ class SpectralConvS2(_S2FilterBase):
             if not (torch.equal(self.ii.cpu(), ref_ii) and torch.equal(self.jj.cpu(), ref_jj)):
                 raise NotImplementedError("ii/jj must be torch.tril_indices(lmax, mmax)")
             self._tril_checked = key
-        w = self.w.detach()
-        if w.dtype != torch.float32 or not w.is_contiguous():
-            w = w.float().contiguous()
-        keep.append(w)
         d.filter_type = N.FILTER_LINEAR
-        d.lin_w = w.data_ptr()
+        d.lin_w = N.f32(self.w, keep).data_ptr()
 
 
 class SpectralAttentionS2(_S2FilterBase):
@@ -469,9 +473,5 @@ class SpectralAttentionS2(_S2FilterBase):
         d.spectral_layers = self.spectral_layers
         d.spec_hidden = self.hidden_size
         for l, p in enumerate(self.w):
-            t = p.detach().float().contiguous()
-            keep.append(t)
-            d.spec_w[l] = t.data_ptr()
-        t = self.wout.detach().float().contiguous()
-        keep.append(t)
-        d.spec_wout = t.data_ptr()
+            d.spec_w[l] = N.f32(p, keep).data_ptr()
+        d.spec_wout = N.f32(self.wout, keep).data_ptr()

@@ -20,7 +20,8 @@ import torch.nn as nn
 
 from .. import _native as N
 from ..harmonics import RealSHT, adopt
-from .layers import MLP, DropPath, SpectralAttentionS2, SpectralConvS2, WeightCache
+from .layers import (MLP, BlockCall, DropPath, SpectralAttentionS2, SpectralConvS2, WeightCache,
+                     block_workspace_size)
 
 
 def _is_real_sht(t):
@@ -118,19 +119,13 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
     def _norm_params(self, norm, keep):
         if not isinstance(norm, nn.InstanceNorm2d) or norm.track_running_stats:
             raise NotImplementedError("the fused block needs InstanceNorm2d(track_running_stats=False)")
-        w = b = None
-        if norm.affine:
-            w = norm.weight.detach().float().contiguous()
-            b = norm.bias.detach().float().contiguous()
-            keep += [w, b]
-        return N.ptr(w), N.ptr(b), float(norm.eps)
+        # weight and bias are None without the affine
+        return N.ptr(N.f32(norm.weight, keep)), N.ptr(N.f32(norm.bias, keep)), float(norm.eps)
 
-    def native_desc(self):
-        keep = []
-        flt = self.filter_layer.filter
-        d, fkeep = flt.native_desc(self.embed_dim_sfno)
-        keep += fkeep
-        C = self.embed_dim_sfno
+    def native_desc(self, C=None):
+        """(descriptor, the fp32 copies it points at); ``C``: the caller's channel count."""
+        assert C is None or C == self.embed_dim_sfno
+        d, keep = self.filter_layer.filter.native_desc(self.embed_dim_sfno)
         if self.concat_skip:
             raise NotImplementedError("concat_skip=True is not on the MI355X path")
         if self.training and not isinstance(self.drop_path, nn.Identity):
@@ -144,10 +139,8 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
             raise NotImplementedError("only nn.GELU() (erf) is fused after the inner skip")
         if hasattr(self, "inner_skip"):
             if isinstance(self.inner_skip, nn.Conv2d):
-                w = self.inner_skip.weight.detach().float().contiguous()
-                b = self.inner_skip.bias
-                b = b.detach().float().contiguous() if b is not None else None
-                keep += [w, b]
+                w = N.f32(self.inner_skip.weight, keep)
+                b = N.f32(self.inner_skip.bias, keep)
                 d.inner_skip, d.skip_w, d.skip_b = N.SKIP_LINEAR, w.data_ptr(), N.ptr(b)
             else:
                 d.inner_skip = N.SKIP_IDENTITY
@@ -167,12 +160,9 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
                 raise NotImplementedError("the block MLP fuses fc1 -> nn.GELU() (erf) -> fc2 only")
             if len(seq) == 5 and self.training:
                 raise NotImplementedError("MLP dropout in training mode is not fused")
-            fc1, fc2 = seq[0], seq[-2] if len(seq) == 5 else seq[2]
-            w1 = fc1.weight.detach().float().contiguous()
-            b1 = fc1.bias.detach().float().contiguous() if fc1.bias is not None else None
-            w2 = fc2.weight.detach().float().contiguous()
-            b2 = fc2.bias.detach().float().contiguous() if fc2.bias is not None else None
-            keep += [w1, b1, w2, b2]
+            fc1, fc2 = self.mlp.convs()
+            w1, b1 = N.f32(fc1.weight, keep), N.f32(fc1.bias, keep)
+            w2, b2 = N.f32(fc2.weight, keep), N.f32(fc2.bias, keep)
             d.has_mlp = 1
             d.mlp_hidden = w1.shape[0]
             d.fc1_w, d.fc1_b, d.fc2_w, d.fc2_b = w1.data_ptr(), N.ptr(b1), w2.data_ptr(), N.ptr(b2)
@@ -188,29 +178,13 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
 
     @N.on_input_device
     def _native_forward(self, x, gamma=None, beta=None, scale=1.0):
-        dtype = x.dtype
-        x = N.require_device_f32(x, "block input")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        assert H == fwd.nlat and W == fwd.nlon and C == self.embed_dim_sfno
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        d, keep = self.native_desc()
-        if gamma is not None:
-            gamma = gamma.detach().float().reshape(B, C).contiguous()
-            beta = beta.detach().float().reshape(B, C).contiguous()
-        L = N.lib()
-        wkey = self.wcache_attach(d, keep, x.device)
-        nbytes = L.msfno_block_workspace_size(d, pf.handle, pi.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(B, C, inv.nlat, inv.nlon, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_block_forward(d, pf.handle, pi.handle, x.data_ptr(), N.ptr(gamma),
-                                      N.ptr(beta), float(scale), out.data_ptr(), B, ws.data_ptr(),
-                                      nbytes, N.stream_of(x.device)),
-                type(self).__name__ + ".forward")
-        self.wcache_commit(wkey)
-        del keep
-        return out.to(dtype)
+        c = BlockCall(self, x)
+        gamma, beta = (N.per_channel_f32(t, c.B, c.C) for t in (gamma, beta))
+        out = c.out()
+        c.run(block_workspace_size, lambda *tail: N.lib().msfno_block_forward(
+            c.d, *c.plans, c.x.data_ptr(), N.ptr(gamma), N.ptr(beta), float(scale),
+            out.data_ptr(), c.B, *tail), type(self).__name__ + ".forward", cache=True)
+        return out.to(c.dtype)
 
     def trainable(self):
         """The parameters that require grad (passed to autograd, whose backward computes
@@ -240,8 +214,7 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
             add(self.inner_skip.weight, "skip_w")
             add(self.inner_skip.bias, "skip_b")
         if hasattr(self, "mlp"):
-            seq = self.mlp.fwd
-            fc1, fc2 = seq[0], seq[-2] if len(seq) == 5 else seq[2]
+            fc1, fc2 = self.mlp.convs()
             add(fc1.weight, "fc1_w")
             add(fc1.bias, "fc1_b")
             add(fc2.weight, "fc2_w")
@@ -265,8 +238,7 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
         from ..harmonics.sht import adjoint_table
         fwd, inv = self._transforms()
         idx = device.index if device.index is not None else torch.cuda.current_device()
-        key = (idx,) + tuple((t.data_ptr(), t._version, t.dtype, str(t.device))
-                             for t in (fwd.weights, inv.pct))
+        key = (idx, N.tensor_key(fwd.weights), N.tensor_key(inv.pct))
         cache = getattr(self, "_adj", None)
         if cache is not None and cache[0] == key:
             return cache[1], cache[2]
@@ -282,31 +254,22 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
     @N.on_input_device
     def native_backward(self, x, dout, gamma=None, beta=None, scale=1.0, need_dx=True,
                         hidden_tap=None, params=(), ws=None):
-        """(dL/dx, dL/dgamma, dL/dbeta) for dout = dL/d(out) (msfno_block_backward_params;
-        the forward is recomputed), plus a list of dL/dp for the parameters ``params``
-        (--retrain-film).  dgamma / dbeta are None for an unfilmed call; dx is None unless
-        need_dx.  ``hidden_tap`` (tests) receives the non-linear filter's recomputed hidden
-        activations, (B, hidden, lmax, mmax) complex per layer, whose ReLU(real) masks this
-        backward applied.  ``ws``: the caller's workspace (uint8 on x's device, holding
-        anything) in place of a fresh one; the call is still given the size this method
-        computes, so ``ws`` must be at least that long."""
-        x = N.require_device_f32(x, "block input")
+        """(dL/dx, dL/dgamma, dL/dbeta, [dL/dp ...]) for dout = dL/d(out)
+        (msfno_block_backward_params; the forward is recomputed), the list holding dL/dp of
+        the parameters ``params`` (--retrain-film; empty without).  dgamma / dbeta are None
+        for an unfilmed call; dx is None unless need_dx.  ``hidden_tap`` (tests) receives
+        the non-linear filter's recomputed hidden activations, (B, hidden, lmax, mmax)
+        complex per layer, whose ReLU(real) masks this backward applied.  ``ws``: the
+        caller's workspace (uint8 on x's device, holding anything) in place of a fresh one;
+        the call is still given the size this method computes, so ``ws`` must be at least
+        that long."""
+        c = BlockCall(self, x, adjoint=True)
         dout = N.require_device_f32(dout, "block output gradient")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        assert H == fwd.nlat and W == fwd.nlon and C == self.embed_dim_sfno
-        assert dout.shape == (B, C, inv.nlat, inv.nlon)
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        fa, ga = self._adjoint_plans(x.device)
-        d, keep = self.native_desc()
-        g = b = dg = db = None
-        if gamma is not None:
-            g = gamma.detach().float().reshape(B, C).contiguous()
-            b = beta.detach().float().reshape(B, C).contiguous()
-            dg = torch.empty(B, C, dtype=torch.float32, device=x.device)
-            db = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        dx = torch.empty_like(x) if need_dx else None
+        B, C = c.B, c.C
+        assert dout.shape == (B, C, c.inv.nlat, c.inv.nlon)
+        g, b = N.per_channel_f32(gamma, B, C), N.per_channel_f32(beta, B, C)
+        dg, db = (c.empty(B, C), c.empty(B, C)) if gamma is not None else (None, None)
+        dx = torch.empty_like(c.x) if need_dx else None
         L = N.lib()
         pgs, pg = [], None
         if params:
@@ -316,43 +279,30 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
                 if id(p) not in fields:
                     raise NotImplementedError(f"no native gradient for parameter {tuple(p.shape)}")
                 f, i = fields[id(p)]
-                t = torch.empty(p.shape, dtype=torch.float32, device=x.device)
+                t = c.empty(p.shape)
                 pgs.append(t)
                 if i is None:
                     setattr(pg, f, t.data_ptr())
                 else:
                     getattr(pg, f)[i] = t.data_ptr()
-            nbytes = L.msfno_block_backward_params_workspace_size(d, pf.handle, pi.handle,
-                                                                  fa.handle, ga.handle, B)
-        else:
-            nbytes = L.msfno_block_backward_workspace_size(d, pf.handle, pi.handle, fa.handle,
-                                                            ga.handle, B)
-        if ws is None:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        elif (ws.dtype != torch.uint8 or ws.device != x.device or ws.dim() != 1
-              or not ws.is_contiguous() or ws.numel() < nbytes):
-            raise ValueError(f"block backward: ws must be {nbytes} contiguous uint8 on {x.device}")
-        N.check(L.msfno_block_backward_params(d, pf.handle, pi.handle, fa.handle, ga.handle,
-                                              x.data_ptr(), N.ptr(g), N.ptr(b), float(scale),
-                                              dout.data_ptr(), N.ptr(dx), N.ptr(dg), N.ptr(db),
-                                              pg, B, ws.data_ptr(), nbytes,
-                                              N.stream_of(x.device)),
-                type(self).__name__ + ".backward")
+        c.run(L.msfno_block_backward_params_workspace_size if params
+              else L.msfno_block_backward_workspace_size,
+              lambda *tail: L.msfno_block_backward_params(
+                  c.d, *c.plans, c.x.data_ptr(), N.ptr(g), N.ptr(b), float(scale),
+                  dout.data_ptr(), N.ptr(dx), N.ptr(dg), N.ptr(db), pg, B, *tail),
+              type(self).__name__ + ".backward", ws=ws)
         if hidden_tap is not None:
             import ctypes
             offs = (ctypes.c_size_t * 8)()
             nl = ctypes.c_int(0)
-            N.check(L.msfno_block_backward_hidden_offsets(d, pf.handle, pi.handle, fa.handle,
-                                                          ga.handle, B, offs, 8, ctypes.byref(nl)),
-                    "hidden offsets")
-            n = B * d.spec_hidden * fwd.lmax * fwd.mmax * 2
-            hs = [ws[offs[l]:offs[l] + 4 * n].view(torch.float32)
-                  .view(B, d.spec_hidden, fwd.lmax, fwd.mmax, 2) for l in range(nl.value)]
+            N.check(L.msfno_block_backward_hidden_offsets(c.d, *c.plans, B, offs, 8,
+                                                          ctypes.byref(nl)), "hidden offsets")
+            fwd, hid = c.fwd, c.d.spec_hidden
+            n = B * hid * fwd.lmax * fwd.mmax * 2
+            hs = [c.ws[offs[l]:offs[l] + 4 * n].view(torch.float32)
+                  .view(B, hid, fwd.lmax, fwd.mmax, 2) for l in range(nl.value)]
             hidden_tap([torch.view_as_complex(h.clone()) for h in hs])
-        del keep
-        if params:
-            return dx, dg, db, pgs
-        return dx, dg, db
+        return dx, dg, db, pgs
 
     def defers_output_affine(self):
         """True for blocks whose output is one per-channel affine of x1 (no MLP, no outer
@@ -365,29 +315,13 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
     def native_forward_deferred(self, x, gamma=None, beta=None, scale=1.0):
         """(x1, affine) with out = affine[0] * x1 + affine[1] per (b, c): the block without
         its output affine pass (msfno_block_forward_deferred)."""
-        x = N.require_device_f32(x, "block input")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        assert H == fwd.nlat and W == fwd.nlon and C == self.embed_dim_sfno
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        d, keep = self.native_desc()
-        if gamma is not None:
-            gamma = gamma.detach().float().reshape(B, C).contiguous()
-            beta = beta.detach().float().reshape(B, C).contiguous()
-        L = N.lib()
-        wkey = self.wcache_attach(d, keep, x.device)
-        nbytes = L.msfno_block_workspace_size(d, pf.handle, pi.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        x1 = torch.empty(B, C, inv.nlat, inv.nlon, dtype=torch.float32, device=x.device)
-        aff = torch.empty(2, B, C, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_block_forward_deferred(d, pf.handle, pi.handle, x.data_ptr(),
-                                               N.ptr(gamma), N.ptr(beta), float(scale),
-                                               x1.data_ptr(), aff.data_ptr(), B, ws.data_ptr(),
-                                               nbytes, N.stream_of(x.device)),
-                type(self).__name__ + ".forward_deferred")
-        self.wcache_commit(wkey)
-        del keep
+        c = BlockCall(self, x)
+        gamma, beta = (N.per_channel_f32(t, c.B, c.C) for t in (gamma, beta))
+        x1, aff = c.out(), c.empty(2, c.B, c.C)
+        c.run(block_workspace_size, lambda *tail: N.lib().msfno_block_forward_deferred(
+            c.d, *c.plans, c.x.data_ptr(), N.ptr(gamma), N.ptr(beta), float(scale),
+            x1.data_ptr(), aff.data_ptr(), c.B, *tail),
+            type(self).__name__ + ".forward_deferred", cache=True)
         return x1, aff
 
 
@@ -406,54 +340,30 @@ class FourierNeuralOperatorBlock_Filmed(FourierNeuralOperatorBlock):
         """sfnonet.py:341-356: norm0(x) -> filter -> + inner_skip(residual) (+ GELU for
         the linear filter) -> norm1, without FiLM, MLP or outer skip
         (msfno_block_global_conv; inference only)."""
-        dtype = x.dtype
-        x = N.require_device_f32(x, "global_conv input")
+        c = BlockCall(self, x, "global_conv input")
         residual = N.require_device_f32(residual, "global_conv residual")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        assert H == fwd.nlat and W == fwd.nlon and C == self.embed_dim_sfno
         if hasattr(self, "inner_skip"):
-            assert residual.shape == x.shape
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        d, keep = self.native_desc()
-        L = N.lib()
-        wkey = self.wcache_attach(d, keep, x.device)
-        nbytes = L.msfno_block_workspace_size(d, pf.handle, pi.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        out = torch.empty(B, C, inv.nlat, inv.nlon, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_block_global_conv(d, pf.handle, pi.handle, x.data_ptr(),
-                                          residual.data_ptr(), out.data_ptr(), B, ws.data_ptr(),
-                                          nbytes, N.stream_of(x.device)),
-                "FourierNeuralOperatorBlock_Filmed.global_conv")
-        self.wcache_commit(wkey)
-        del keep
-        return out.to(dtype)
+            assert residual.shape == c.x.shape
+        out = c.out()
+        c.run(block_workspace_size, lambda *tail: N.lib().msfno_block_global_conv(
+            c.d, *c.plans, c.x.data_ptr(), residual.data_ptr(), out.data_ptr(), c.B, *tail),
+            "FourierNeuralOperatorBlock_Filmed.global_conv", cache=True)
+        return out.to(c.dtype)
 
     @N.on_input_device
     def native_film_backward(self, x, gamma, beta, scale, dout):
         """(dL/dgamma, dL/dbeta) of this block for dout = dL/d(out), SFNO weights frozen
         (msfno_block_film_backward; the forward up to x1 is recomputed)."""
-        x = N.require_device_f32(x, "block input")
+        c = BlockCall(self, x)
         dout = N.require_device_f32(dout, "block output gradient")
-        B, C, H, W = x.shape
-        fwd, inv = self._transforms()
-        pf = fwd._plan(x.device)
-        pi = inv._plan(x.device)
-        d, keep = self.native_desc()
-        g = gamma.detach().float().reshape(B, C).contiguous()
-        b = beta.detach().float().reshape(B, C).contiguous()
+        g, b = N.per_channel_f32(gamma, c.B, c.C), N.per_channel_f32(beta, c.B, c.C)
+        dg, db = c.empty(c.B, c.C), c.empty(c.B, c.C)
         L = N.lib()
-        nbytes = L.msfno_block_film_backward_workspace_size(d, pf.handle, pi.handle, B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        dg = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        db = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        N.check(L.msfno_block_film_backward(d, pf.handle, pi.handle, x.data_ptr(), g.data_ptr(),
-                                            b.data_ptr(), float(scale), dout.data_ptr(),
-                                            dg.data_ptr(), db.data_ptr(), B, ws.data_ptr(),
-                                            nbytes, N.stream_of(x.device)),
-                "FourierNeuralOperatorBlock_Filmed.backward")
-        del keep
+        c.run(L.msfno_block_film_backward_workspace_size,
+              lambda *tail: L.msfno_block_film_backward(
+                  c.d, *c.plans, c.x.data_ptr(), g.data_ptr(), b.data_ptr(), float(scale),
+                  dout.data_ptr(), dg.data_ptr(), db.data_ptr(), c.B, *tail),
+              "FourierNeuralOperatorBlock_Filmed.backward")
         return dg, db
 
 
@@ -488,10 +398,8 @@ class _FilmedBlockFn(torch.autograd.Function):
         dx, pgs = None, []
         if ctx.needs_input_grad[0] or wanted:
             # dL/dx too (film_layers > 1, repeat_film: filmed blocks back to back)
-            res = ctx.blk.native_backward(x, dout, gamma, beta, ctx.scale,
-                                          need_dx=ctx.needs_input_grad[0], params=wanted)
-            dx, dg, db = res[:3]
-            pgs = res[3] if wanted else []
+            dx, dg, db, pgs = ctx.blk.native_backward(
+                x, dout, gamma, beta, ctx.scale, need_dx=ctx.needs_input_grad[0], params=wanted)
             dx = dx.to(x.dtype) if dx is not None else None
         else:
             dg, db = ctx.blk.native_film_backward(x, gamma, beta, ctx.scale, dout)
@@ -514,9 +422,10 @@ class _BlockFn(torch.autograd.Function):
     def backward(ctx, dout):
         (x,) = ctx.saved_tensors
         wanted = _wanted(ctx, 2, ctx.params)
-        res = ctx.blk.native_backward(x, dout, need_dx=ctx.needs_input_grad[0], params=wanted)
-        dx = res[0].to(x.dtype) if res[0] is not None else None
-        return (dx, None) + _scatter(ctx.params, wanted, res[3] if wanted else [])
+        dx, _, _, pgs = ctx.blk.native_backward(x, dout, need_dx=ctx.needs_input_grad[0],
+                                                params=wanted)
+        dx = dx.to(x.dtype) if dx is not None else None
+        return (dx, None) + _scatter(ctx.params, wanted, pgs)
 
 
 def _trunc_normal_init(m):

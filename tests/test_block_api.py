@@ -82,3 +82,29 @@ def test_layer_norm_network_is_refused_at_construction():
         FourierNeuralOperatorNet("cpu", None, img_size=(33, 64), scale_factor=4, in_chans=5,
                                  out_chans=5, embed_dim_sfno=16, num_layers=4,
                                  normalization_layer="layer_norm")
+
+
+@pytest.mark.parametrize("drop_rate", [0.1, 0.0], ids=["dropout", "plain"])
+def test_mlp_descriptor_finds_fc1_fc2_with_and_without_dropout(drop_rate):
+    """MLP.fwd is (fc1, act, fc2) or, with drop_rate > 0, (fc1, act, drop, fc2, drop)
+    (layers.py:161-178).  In eval mode both describe the same MLP: the descriptor's widths
+    and its four pointers are those of the module's own Conv2d tensors (fp32 contiguous
+    parameters are passed as they are), found by MLP.convs().  Training-mode dropout is not
+    fused and is refused."""
+    import torch.nn as nn
+    from msfno_amd.sfno import MLP
+    m = MLP(8, 16, 8, drop_rate=drop_rate).eval()
+    assert len(m.fwd) == (5 if drop_rate else 3)
+    fc1, fc2 = m.convs()
+    assert isinstance(fc1, nn.Conv2d) and isinstance(fc2, nn.Conv2d)
+    assert fc1 is m.fwd[0] and fc2 is m.fwd[3 if drop_rate else 2]
+    d, keep = m.native_desc()
+    assert (d.Cin, d.Hid, d.Cout) == (8, 16, 8)
+    assert d.fc1_w == fc1.weight.data_ptr() and d.fc1_b == fc1.bias.data_ptr()
+    assert d.fc2_w == fc2.weight.data_ptr() and d.fc2_b == fc2.bias.data_ptr()
+    m.train()
+    if drop_rate:
+        with pytest.raises(NotImplementedError, match="dropout in training mode"):
+            m.native_desc()
+    else:
+        m.native_desc()

@@ -74,6 +74,37 @@ def test_native_mlp_concat_and_broadcast_addend():
     assert (got - want).abs().max().item() < 1e-5 * max(1.0, want.abs().max().item())
 
 
+@pytest.mark.parametrize("cin,hid,cout,fused", [(73, 64, 256, True), (12, 24, 9, False)],
+                         ids=["fused_width", "two_gemm"])
+def test_mlp_with_dropout_modules_in_eval_equals_plain_mlp(cin, hid, cout, fused):
+    """A stand-alone MLP(drop_rate > 0) in eval mode (fc1, act, drop, fc2, drop) and a plain
+    MLP carrying the same four tensors run the same kernels on the same bytes: the outputs,
+    dL/dx and the four parameter gradients are bit-equal, on the fused x3h kernel and on the
+    two-GEMM path (B = 2, a 6 x 10 grid)."""
+    from msfno_amd import _native as N
+    from msfno_amd.sfno import MLP
+    torch.manual_seed(11)
+    drop = MLP(cin, hid, cout, drop_rate=0.1).eval()
+    plain = MLP(cin, hid, cout).eval()
+    assert len(drop.fwd) == 5 and len(plain.fwd) == 3
+    for a, b in zip(plain.convs(), drop.convs()):
+        a.load_state_dict(b.state_dict())
+    x0 = torch.randn(2, cin, 6, 10)
+    res = []
+    for m in (drop.to(DEV), plain.to(DEV)):
+        assert bool(N.lib().msfno_mlp_fused_supported(m.native_desc()[0])) == fused
+        x = x0.to(DEV).requires_grad_()
+        out = m(x)
+        out.sum().backward()
+        fc1, fc2 = m.convs()
+        res.append([out.detach(), x.grad, fc1.weight.grad, fc1.bias.grad, fc2.weight.grad,
+                    fc2.bias.grad])
+    names = ("out", "dx", "dfc1_w", "dfc1_b", "dfc2_w", "dfc2_b")
+    for name, a, b in zip(names, *res):
+        assert a is not None and torch.isfinite(a).all(), name
+        assert torch.equal(a, b), name
+
+
 def _sharded_net(net, x, world, sst=None, scale=1.0, inner="shard"):
     from msfno_amd.sfno import LatBandBlock, LatBandNet, LocalGroup
     shards = [LatBandNet(net, r, world, inner=inner) for r in range(world)]
