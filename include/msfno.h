@@ -460,6 +460,71 @@ int msfno_ens_crps_backward(const float* ens, long long member_stride, const flo
                             void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Graph-convolution FiLM generator (MSFNO/Models/gcn/gcn.py:96-167 GCN_custom,
+ * layers.py:8-43 GraphConvolution; the Python mirror is msfno_amd/filmgen.py): the network
+ * that turns the ocean points of an SST field into the FiLM vector, and its backward.  Per
+ * sample b, all fp32, with leaky the LeakyReLU of slope 0.01 and A any real N x N sparse
+ * matrix (unsymmetric, unnormalised, empty rows allowed):
+ *   h_1     = leaky(A (x0 W0) + b0)                       x0 (B, N, Fin), W0 (Fin, hidden)
+ *   h_{l+1} = h_l + leaky(A (h_l W_l) + b_l), l = 1..depth   W_l (hidden, hidden), input-major
+ *   y       = mean_nodes(h_last) Wh^T + bh                Wh (out, hidden), y (B, out)
+ * the per-sample math the reference states in layers.py:37-39 (its executed code takes
+ * sample 0 only and runs at depth 0 only).  A is CSR with values on the device (row_ptr
+ * N + 1 int32, col and val nnz, every col in [0, N): the caller's contract, it is not
+ * checked); t_* is the CSR of A^T, needed by msfno_gcn_backward only.  The K = hidden
+ * products run on the split-precision MFMA engine, the conv1 layer as (A x0) W0.
+ *   msfno_gcn_forward: y from x0.  With train != 0 it keeps every layer's input and
+ *     pre-activation in the workspace, and msfno_gcn_backward on the same, untouched
+ *     workspace (sized with train = 1, same B, graph and descriptor) gives the gradients
+ *     of L for dy = dL/dy (B, out): every tensor of grads, and dx0 (B, N, Fin) unless NULL.
+ * No atomics: every sum has a fixed order (a row's neighbours in CSR order; column sums
+ * per lane, per workgroup, then in fp64 over the chunks), so results are bitwise
+ * reproducible.  Every word of y, of every gradient and of dx0 is written by every call;
+ * the workspace may hold anything on entry to the forward; nothing allocates, synchronises
+ * or memsets, so the calls record into a graph.  MSFNO_EINVAL for null required pointers,
+ * an extent below 1, parameters or a workspace off the 16-byte grid; MSFNO_EUNSUPPORTED for
+ * hidden % 4 != 0, Fin > 16, depth > MSFNO_GCN_MAX_DEPTH or B * N > 2^21;
+ * MSFNO_EWORKSPACE for a short workspace; all before any launch.
+ * msfno_gcn_workspace_size returns 0 for sizes the calls refuse.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+#define MSFNO_GCN_MAX_DEPTH 16
+typedef struct msfno_gcn_graph {
+  int N;
+  long long nnz;
+  const int* row_ptr;
+  const int* col;
+  const float* val;
+  const int* t_row_ptr; /* A^T; all three may be NULL for forward-only use */
+  const int* t_col;
+  const float* t_val;
+} msfno_gcn_graph;
+typedef struct msfno_gcn_desc {
+  int Fin, hidden, depth, out;
+  const float* conv1_w; /* (Fin, hidden) */
+  const float* conv1_b; /* (hidden) */
+  const float* conv_w[MSFNO_GCN_MAX_DEPTH]; /* (hidden, hidden) each */
+  const float* conv_b[MSFNO_GCN_MAX_DEPTH];
+  const float* head_w; /* (out, hidden) */
+  const float* head_b; /* (out) */
+} msfno_gcn_desc;
+typedef struct msfno_gcn_grads { /* shapes as in msfno_gcn_desc; all required */
+  float* conv1_w;
+  float* conv1_b;
+  float* conv_w[MSFNO_GCN_MAX_DEPTH];
+  float* conv_b[MSFNO_GCN_MAX_DEPTH];
+  float* head_w;
+  float* head_b;
+} msfno_gcn_grads;
+size_t msfno_gcn_workspace_size(int B, int N, int Fin, int hidden, int depth, int out, int train);
+int msfno_gcn_forward(const msfno_gcn_graph* g, const msfno_gcn_desc* d, const float* x0,
+                      float* y /* (B, out) */, int B, int train, void* ws, size_t ws_bytes,
+                      void* stream);
+int msfno_gcn_backward(const msfno_gcn_graph* g, const msfno_gcn_desc* d, const float* dy,
+                       const msfno_gcn_grads* grads, float* dx0 /* (B, N, Fin) or NULL */, int B,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Per-degree power spectrum of spherical-harmonic coefficients and its gradient: the
  * middle step of the reference's spectral losses (MSFNO/Models/losses.py:158-232,
  * spectral_l2loss_sphere, spectral_loss_sphere, h1loss_sphere; the Python mirror is

@@ -177,6 +177,40 @@ int launch_ens_sums(const float* ens, int64_t mstride, const float* tar, const f
 int launch_ens_crps_backward(const float* ens, int64_t mstride, const float* tar,
                              const float* w_lat, const float* g, float kappa, float* dens,
                              int64_t dstride, int M, int S, int nlat, int nlon, hipStream_t s);
+// ---- graph.hip: the graph-convolution FiLM generator (gcn.cpp) -----------------------------
+// node-major activations (nb N, hid), hid % 4 == 0, 16-byte aligned; CSR (rp N + 1, ci, av).
+// part (gcn_partial_bytes, may hold anything on entry) receives the fixed-order column
+// partials of `out`: per sample (the pool), or over all samples (a bias gradient);
+// launch_gcn_colsum_combine(part, out, slabs = nb hid or hid, chunks = gcn_chunks(N) or
+// nb gcn_chunks(N)) finishes them in fp64
+constexpr int kGcnRows = 32;  // nodes per unit
+int gcn_chunks(int N);
+size_t gcn_partial_bytes(int nb, int N, int hid);
+// bias given: out = resid + leaky(A S + bias) (resid or null), Pout (or null) = A S + bias;
+// bias null: out = A S
+int launch_gcn_aggregate(const int* rp, const int* ci, const float* av, const float* S,
+                         const float* bias, const float* resid, float* out, float* Pout,
+                         float* part, int nb, int N, int hid, hipStream_t s);
+// out = leaky(ax W0 + b0), ax (nb N, Fin) the aggregated narrow input, W0 (Fin, hid)
+int launch_gcn_expand(const float* ax, const float* W0, const float* b0, float* out, float* Pout,
+                      float* part, int nb, int N, int Fin, int hid, hipStream_t s);
+// dP = dH leaky'(P) (slope where P <= 0), part: the partials of sum_(b, n) dP
+int launch_gcn_act_grad(const float* dH, const float* P, float* dP, float* part, int nb, int N,
+                        int hid, hipStream_t s);
+int launch_gcn_colsum_combine(const float* part, float* out, int slabs, int chunks, hipStream_t s);
+// out = A x on rows of F floats, any F (the first layer's input, its gradient)
+int launch_gcn_spmm_narrow(const int* rp, const int* ci, const float* av, const float* x,
+                           float* out, int nb, int N, int F, hipStream_t s);
+// dax (rows, Fin) = dP (rows, hid) W0^T
+int launch_gcn_dax(const float* dP, const float* W0, float* dax, int64_t rows, int hid, int Fin,
+                   hipStream_t s);
+// y (nb, out) = (poolsum / N) Wh^T + bh, and its backward (dpool includes the 1 / N)
+int launch_gcn_head(const float* poolsum, const float* Wh, const float* bh, float* y, int nb,
+                    int hid, int out, int N, hipStream_t s);
+int launch_gcn_head_bwd(const float* dy, const float* poolsum, const float* Wh, float* dpool,
+                        float* dWh, float* dbh, int nb, int hid, int out, int N, hipStream_t s);
+// dH[(b, n)][:] = dpool[b][:]
+int launch_gcn_bcast(const float* dpool, float* dH, int nb, int N, int hid, hipStream_t s);
 // ---- spectrum.hip: per-degree power spectrum and its gradient ----------------------------
 // coeffs (rows, mmax) complex interleaved, 8-byte aligned, rows = N * lmax:
 // power[r] = |c[r][0]|^2 + 2 sum_{m >= 1} |c[r][m]|^2

@@ -81,6 +81,40 @@ class BandIO(ctypes.Structure):
     ]
 
 
+GCN_MAX_DEPTH = 16
+
+
+class GcnGraph(ctypes.Structure):
+    """Mirror of ``msfno_gcn_graph`` (include/msfno.h)."""
+
+    _fields_ = [
+        ("N", _i), ("nnz", ctypes.c_longlong),
+        ("row_ptr", _vp), ("col", _vp), ("val", _vp),
+        ("t_row_ptr", _vp), ("t_col", _vp), ("t_val", _vp),
+    ]
+
+
+class GcnDesc(ctypes.Structure):
+    """Mirror of ``msfno_gcn_desc`` (include/msfno.h)."""
+
+    _fields_ = [
+        ("Fin", _i), ("hidden", _i), ("depth", _i), ("out", _i),
+        ("conv1_w", _vp), ("conv1_b", _vp),
+        ("conv_w", _vp * GCN_MAX_DEPTH), ("conv_b", _vp * GCN_MAX_DEPTH),
+        ("head_w", _vp), ("head_b", _vp),
+    ]
+
+
+class GcnGrads(ctypes.Structure):
+    """Mirror of ``msfno_gcn_grads`` (include/msfno.h)."""
+
+    _fields_ = [
+        ("conv1_w", _vp), ("conv1_b", _vp),
+        ("conv_w", _vp * GCN_MAX_DEPTH), ("conv_b", _vp * GCN_MAX_DEPTH),
+        ("head_w", _vp), ("head_b", _vp),
+    ]
+
+
 _ip = ctypes.POINTER(_i)
 _llp = ctypes.POINTER(ctypes.c_longlong)
 
@@ -155,6 +189,11 @@ SIGNATURES = [
                             _vp]),
     ("msfno_ens_crps_backward", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _vp,
                                      ctypes.c_longlong, _i, _i, _i, _i, _vp]),
+    ("msfno_gcn_workspace_size", _sz, [_i, _i, _i, _i, _i, _i, _i]),
+    ("msfno_gcn_forward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp, _vp, _i,
+                               _i, _vp, _sz, _vp]),
+    ("msfno_gcn_backward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp,
+                                ctypes.POINTER(GcnGrads), _vp, _i, _vp, _sz, _vp]),
     ("msfno_spectrum_power", _i, [_vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
     ("msfno_spectrum_power_backward", _i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
     ("msfno_band_partition", _i, [_i, _i, _i, _i, _ip, _ip]),

@@ -628,10 +628,12 @@ class FourierNeuralOperatorNet(nn.Module):
 
 class FourierNeuralOperatorNet_Filmed(FourierNeuralOperatorNet):
     """Mirror of sfnonet.py:699-860: the last ``film_layers`` blocks (every block
-    with cfg.repeat_film) are FourierNeuralOperatorBlock_Filmed.  The FiLM
-    generator (Film_wrapper: GCN / ViT / MAE over SST fields, :862-) is outside
-    the MI355X hot path: pass ``film_gen`` (any module mapping sst to
-    (B, 2, film_layers, C)) or call forward with the modulation tensor itself as
+    with cfg.repeat_film) are FourierNeuralOperatorBlock_Filmed.  ``film_gen`` is the
+    FiLM generator (Film_wrapper, :862-): ``msfno_amd.filmgen.Film_wrapper`` is the native
+    mirror of the reference's default (GCN_custom over the ocean points of the SST grid,
+    forward and backward in libmsfno); any other module mapping sst to
+    (B, 2, film_layers, C) works too (the PyG gcn, ViT and MAE generators are not
+    mirrored).  With ``film_gen=None`` forward takes the modulation tensor itself as
     ``sst`` (film_mod[:, 0] = gamma, film_mod[:, 1] = beta, :812)."""
 
     def __init__(self, device, cfg, mlp_ratio=2.0, drop_rate=0.0, sparsity_threshold=0.0,
