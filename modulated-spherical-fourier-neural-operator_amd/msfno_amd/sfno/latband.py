@@ -448,11 +448,11 @@ class LatBandBlock:
             tabs.append(t)
         self.plan.load(tabs[0], tabs[1], key)
 
-    def _linear_weight(self, w):
+    def _linear_weight(self, w, train=False):
         """This rank's slice w[:, :, modes, :] of the per-mode weight (cached until
         the parameter changes); the whole weight when the rank owns every mode."""
-        key = N.tensor_key(w)
-        if self._lin is not None and self._lin[0] == key:
+        key = (N.tensor_key(w), getattr(self.block, "_wcache_epoch", 0))
+        if not train and self._lin is not None and self._lin[0] == key:
             return self._lin[1]
         modes = self.plan.linear_modes()
         # the contraction reads fp32 (C, C, T, 2) contiguous, as _fill_desc passes it
@@ -462,7 +462,8 @@ class LatBandBlock:
         else:
             idx = torch.tensor(modes, dtype=torch.long, device=w.device)
             local = wf.index_select(2, idx).contiguous()
-        self._lin = (key, local)
+        # like the block's weight images, not kept across a call that trains (wcache_attach)
+        self._lin = None if train else (key, local)
         return local
 
     def _buffers(self, B, C, slot):
@@ -496,14 +497,15 @@ class LatBandBlock:
             raise ValueError(f"x_local must be (B, {self.block.embed_dim_sfno}, {len(self.rows)}, "
                              f"{self.nlon}), got {tuple(x.shape)}")
         self._tables()
+        train = self.block.wcache_trains()
         d, keep = self.block.native_desc()
         if d.filter_type == N.FILTER_LINEAR:
-            wl = self._linear_weight(self.block.filter_layer.filter.w)
+            wl = self._linear_weight(self.block.filter_layer.filter.w, train)
             d.lin_w = wl.data_ptr()
             keep.append(wl)
         gamma, beta = N.per_channel_f32(gamma, B, C), N.per_channel_f32(beta, B, C)
         L = N.lib()
-        wkey = self.block.wcache_attach(d, keep, x.device)  # prepared-weight images
+        wkey = self.block.wcache_attach(d, keep, x.device, train)  # prepared-weight images
         bufs = self._buffers(B, C, slot)
         nbytes = L.msfno_band_workspace_size(d, self.plan.handle, B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -629,10 +631,17 @@ class LatBandNet:
 
     def _pos_local(self, device):
         pe = self.net.pos_embed
-        key = (pe.data_ptr(), pe._version, str(device))
-        if self._pos is None or self._pos[0] != key:
+        # the rule of WeightCache.wcache_attach: no reuse in grad mode while pos_embed trains
+        # (a write through .data leaves _version alone); for a frozen one,
+        # invalidate_weight_cache of the encoder, which net.apply reaches, drops the copy
+        train = torch.is_grad_enabled() and pe.requires_grad
+        key = (pe.data_ptr(), pe._version, str(device),
+               getattr(self.net.encoder, "_wcache_epoch", 0))
+        if train or self._pos is None or self._pos[0] != key:
             idx = torch.tensor(self.rows, dtype=torch.long, device=pe.device)
-            self._pos = (key, pe.detach().index_select(2, idx).to(device).contiguous())
+            local = pe.detach().index_select(2, idx).to(device).contiguous()
+            self._pos = None if train else (key, local)
+            return local
         return self._pos[1]
 
     def stages(self, x, sst=None, scale=1.0, slot=0):
@@ -646,7 +655,8 @@ class LatBandNet:
             film_mod = net.film_gen(sst) if net.film_gen is not None else sst
             gamma, beta = film_mod[:, 0], film_mod[:, 1]
         residual = x
-        h = net.encoder.native_forward(x, addend=self._pos_local(x.device))
+        h = net.encoder.native_forward(x, addend=self._pos_local(x.device),
+                                       train=net.encoder.wcache_trains())
         h = net.pos_drop(h)  # sfnonet.py:674 / 827 (identity in eval)
 
         def film_args(i):

@@ -59,17 +59,42 @@ class WeightCache:
         """The prepared images depend only on the module's own weights: key on the
         Parameters themselves (data_ptr, _version, dtype), not on the fp32 copies the
         descriptor points at (those are fresh tensors, version 0, often at a reused
-        address)."""
+        address).  ``_version`` sees the unfused optimizers' steps, load_state_dict and
+        in-place ops under no_grad; it does not see writes through ``p.data`` nor, on the
+        GPU, the step of ``Adam(fused=True)`` (see ``wcache_trains``)."""
         return (str(device), nbytes) + tuple(
             (p.data_ptr(), p._version, p.dtype) for p in self.parameters())
 
-    def wcache_attach(self, d, keep, device):
+    def wcache_trains(self):
+        """True for a call in grad mode of a module with a trainable parameter: such a call
+        rebuilds the images and leaves them marked invalid, since the weights of a module
+        in training change between calls in ways no key sees (``p.data.copy_``,
+        ``p.data = t``: a sharded optimizer's broadcast, an EMA swap; a fused optimizer's
+        step).  The autograd Functions, whose forward runs with grad mode off, state the
+        same as ``bool(params)``: they are entered only in grad mode, with the module's
+        trainable parameters."""
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def invalidate_weight_cache(self):
+        """Forget the prepared weight images: the next call rebuilds them.  For weights of
+        a frozen module changed through ``p.data`` (an EMA swap in eval), which leaves the
+        key as it was; ``net.apply(lambda m: getattr(m, "invalidate_weight_cache",
+        lambda: None)())`` reaches every cache of a network.  The buffer and its stream
+        event stay, so the rebuild is ordered after the last reader.  ``_wcache_epoch``
+        counts these calls for the copies kept outside the module (the latitude-band
+        shards' weight slice and pos_embed rows)."""
+        self._wcache_key = None
+        self._wcache_epoch = getattr(self, "_wcache_epoch", 0) + 1
+
+    def wcache_attach(self, d, keep, device, train=False):
         """Point the descriptor at this module's prepared-weight cache (bf16x3 weight
         images, the descriptor's wcache) and mark it valid when the weights are
-        unchanged since it was filled.  Returns the key to pass to wcache_commit once
+        unchanged since it was filled.  Returns the token to pass to wcache_commit once
         the native call has been issued.  In-place weight updates bump _version, so
         the next call rebuilds the images; a HIP graph captured with a valid cache
-        replays without the preparation (weights frozen, as in Rollout).
+        replays without the preparation (weights frozen, as in Rollout).  With ``train``
+        (``wcache_trains``) the images are rebuilt whatever the key says and stay invalid
+        after the call, so the next call without grad mode (validation) rebuilds once too.
 
         Stream safety: the images were written (and last read) on the stream of the
         previous committed call; a call on another stream first waits for that call's
@@ -93,24 +118,29 @@ class WeightCache:
         if ev is not None and ev[0] != cur.cuda_stream \
                 and not torch.cuda.is_current_stream_capturing():
             cur.wait_event(ev[1])
-        key = self._wcache_key_of(device, nbytes)
         d.wcache = buf.data_ptr()
+        if train:
+            self._wcache_key = None
+            d.wcache_valid = 0
+            return (None,)
+        key = self._wcache_key_of(device, nbytes)
         d.wcache_valid = int(key == getattr(self, "_wcache_key", None))
-        return key
+        return (key,)
 
-    def wcache_commit(self, key):
-        """Mark the images valid after the native call that (re)built them.  Never
+    def wcache_commit(self, token):
+        """Record the native call that read (and maybe rebuilt) the images, and mark them
+        valid under the token's key (none after a ``train`` call).  Never
         while the stream is being captured: the preparation then lives only in the
         graph, and the buffer has not been written yet (a capture that found the
         images valid leaves the key as it was)."""
-        if key is None or torch.cuda.is_current_stream_capturing():
+        if token is None or torch.cuda.is_current_stream_capturing():
             return
         dev = self._wcache_buf.device
         cur = torch.cuda.current_stream(dev)
         e = torch.cuda.Event()
         e.record(cur)
         self._wcache_event = (cur.cuda_stream, e)
-        self._wcache_key = key
+        self._wcache_key = token[0]
 
 
 class BlockCall:
@@ -142,12 +172,13 @@ class BlockCall:
         """The (B, C, nlat, nlon) result on the inverse transform's grid."""
         return self.empty(self.B, self.C, self.inv.nlat, self.inv.nlon)
 
-    def run(self, size_fn, entry, what, cache=False, ws=None):
+    def run(self, size_fn, entry, what, cache=False, ws=None, train=False):
         """Issue the call: with ``cache`` the module's prepared-weight cache attached before
-        and committed after; the workspace sized by the entry point's own ``size_fn`` and
-        allocated here, or the caller's ``ws`` checked against that size (it stays in
-        ``self.ws``); ``entry(ws_ptr, ws_bytes, stream)`` makes the C call."""
-        wkey = self.mod.wcache_attach(self.d, self.keep, self.device) if cache else None
+        and committed after (``train``: rebuilt and left invalid, WeightCache.wcache_attach);
+        the workspace sized by the entry point's own ``size_fn`` and allocated here, or the
+        caller's ``ws`` checked against that size (it stays in ``self.ws``);
+        ``entry(ws_ptr, ws_bytes, stream)`` makes the C call."""
+        wkey = self.mod.wcache_attach(self.d, self.keep, self.device, train) if cache else None
         nbytes = size_fn(self.d, *self.plans, self.B)
         if ws is None:
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
@@ -229,9 +260,10 @@ class MLP(WeightCache, nn.Module):
     def _wcache_bytes(self, d):
         return N.lib().msfno_mlp_wcache_size(d)
 
-    def _forward(self, entry, affine, what, x, x2, addend):
+    def _forward(self, entry, affine, what, x, x2, addend, train=False):
         """The body of both forwards: ``entry`` is msfno_mlp_forward (``affine`` empty) or
-        msfno_mlp_forward_affine (``affine`` its two extra pointers, after x)."""
+        msfno_mlp_forward_affine (``affine`` its two extra pointers, after x); ``train`` as
+        in WeightCache.wcache_attach."""
         dtype = x.dtype
         x = N.require_device_f32(x, "MLP input")
         B, Cin, H, W = x.shape
@@ -249,7 +281,7 @@ class MLP(WeightCache, nn.Module):
             assert addend.shape[1:] == (d.Cout, H, W)
             bstride = 0 if addend.shape[0] == 1 else d.Cout * H * W
         P = H * W
-        wkey = self.wcache_attach(d, keep, x.device)
+        wkey = self.wcache_attach(d, keep, x.device, train)
         nbytes = N.lib().msfno_mlp_workspace_size(d, B, P)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty(B, d.Cout, H, W, dtype=torch.float32, device=x.device)
@@ -259,11 +291,13 @@ class MLP(WeightCache, nn.Module):
         return out.to(dtype)
 
     @N.on_input_device
-    def native_forward(self, x, x2=None, addend=None):
+    def native_forward(self, x, x2=None, addend=None, train=False):
         """out = fc2(GELU(fc1(cat(x, x2)))) (+ addend, broadcast over the batch when its
         leading dimension is 1) in two MFMA GEMMs (msfno_mlp_forward); the channel
-        concatenation is consumed in place (sfnonet.py:680-686)."""
-        return self._forward(N.lib().msfno_mlp_forward, (), "MLP.forward", x, x2, addend)
+        concatenation is consumed in place (sfnonet.py:680-686).  ``train``: the weight
+        images are rebuilt and left invalid (WeightCache.wcache_attach)."""
+        return self._forward(N.lib().msfno_mlp_forward, (), "MLP.forward", x, x2, addend,
+                             train)
 
     @N.on_input_device
     def native_forward_affine(self, x, x_scale, x_shift, x2=None, addend=None):
@@ -334,13 +368,15 @@ class _MLPFn(torch.autograd.Function):
         ctx.mlp, ctx.params = mlp, params
         if addend is not None:
             ctx.addend_shape, ctx.addend_dtype = addend.shape, addend.dtype
-        ctx.save_for_backward(x, x2)
-        return mlp.native_forward(x, x2=x2, addend=addend)
+        # the parameters too: autograd then refuses a backward after an in-place change
+        # of one (the backward recomputes the forward from the weights as they are then)
+        ctx.save_for_backward(x, x2, *params)
+        return mlp.native_forward(x, x2=x2, addend=addend, train=bool(params))
 
     @staticmethod
     def backward(ctx, dy):
         from .sfnonet import _scatter, _wanted
-        x, x2 = ctx.saved_tensors
+        x, x2 = ctx.saved_tensors[:2]
         wanted = _wanted(ctx, 4, ctx.params)
         need2 = bool(ctx.needs_input_grad[1])  # the decoder's big skip (the network input)
         dx, dx2, pgs = None, None, []

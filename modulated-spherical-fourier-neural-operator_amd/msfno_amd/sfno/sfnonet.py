@@ -177,13 +177,15 @@ class FourierNeuralOperatorBlock(WeightCache, nn.Module):
         return N.lib().msfno_block_wcache_size(d)
 
     @N.on_input_device
-    def _native_forward(self, x, gamma=None, beta=None, scale=1.0):
+    def _native_forward(self, x, gamma=None, beta=None, scale=1.0, train=False):
+        """``train``: the weight images are rebuilt and left invalid (wcache_attach)."""
         c = BlockCall(self, x)
         gamma, beta = (N.per_channel_f32(t, c.B, c.C) for t in (gamma, beta))
         out = c.out()
         c.run(block_workspace_size, lambda *tail: N.lib().msfno_block_forward(
             c.d, *c.plans, c.x.data_ptr(), N.ptr(gamma), N.ptr(beta), float(scale),
-            out.data_ptr(), c.B, *tail), type(self).__name__ + ".forward", cache=True)
+            out.data_ptr(), c.B, *tail), type(self).__name__ + ".forward", cache=True,
+            train=train)
         return out.to(c.dtype)
 
     def trainable(self):
@@ -388,12 +390,14 @@ class _FilmedBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, scale, blk, *params):
         ctx.blk, ctx.scale, ctx.params = blk, scale, params
-        ctx.save_for_backward(x, gamma, beta)
-        return blk._native_forward(x, gamma, beta, scale)
+        # the parameters too: autograd then refuses a backward after an in-place change
+        # of one (the backward recomputes the forward from the weights as they are then)
+        ctx.save_for_backward(x, gamma, beta, *params)
+        return blk._native_forward(x, gamma, beta, scale, train=bool(params))
 
     @staticmethod
     def backward(ctx, dout):
-        x, gamma, beta = ctx.saved_tensors
+        x, gamma, beta = ctx.saved_tensors[:3]
         wanted = _wanted(ctx, 5, ctx.params)
         dx, pgs = None, []
         if ctx.needs_input_grad[0] or wanted:
@@ -415,12 +419,12 @@ class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, *params):
         ctx.blk, ctx.params = blk, params
-        ctx.save_for_backward(x)
-        return blk._native_forward(x)
+        ctx.save_for_backward(x, *params)  # as in _FilmedBlockFn: their versions are checked
+        return blk._native_forward(x, train=bool(params))
 
     @staticmethod
     def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
+        x = ctx.saved_tensors[0]
         wanted = _wanted(ctx, 2, ctx.params)
         dx, _, _, pgs = ctx.blk.native_backward(x, dout, need_dx=ctx.needs_input_grad[0],
                                                 params=wanted)
