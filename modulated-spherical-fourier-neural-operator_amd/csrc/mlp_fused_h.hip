@@ -594,8 +594,17 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
   o[MH_PLANE / 2] = t1;
 }
 
+// (MH_PK: this unit is built without packed FP32 for the block MLP, Makefile NOPK_SRCS; the
+// two skip kernels keep it, and with it the code they had: without, skip_hp_kernel
+// measured 1 % slower and took 20 bytes more scratch, profiles/r11_mlp_io)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MH_PK __attribute__((target("packed-fp32-ops")))
+#else
+#define MH_PK  // (a device feature: the host pass does not know it)
+#endif
+
 template <int NS, int MINB>
-__global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
+MH_PK __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
   constexpr int W = 4;
   constexpr int RING_BYTES = NS * MH_SLICE * 2;
   __shared__ __attribute__((aligned(16))) char lds_raw[RING_BYTES + 2 * MH_C * 4];
@@ -759,7 +768,7 @@ struct SkipHPParams {
   int tiles;
 };
 
-__global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
+MH_PK __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
   constexpr int NS = SP_NS;
   __shared__ __attribute__((aligned(16))) char lds[SP_LDS];
   float* const epi_all = reinterpret_cast<float*>(lds + NS * SP_SLOT);
