@@ -816,11 +816,11 @@ __global__ __launch_bounds__(64 * WV) void fft_r2c_dma_kernel(const float* __res
 
 // inverse: Yn row (mmax bins, DMA from the 16-B aligned address below the row
 // start) and, with ADD, the skip-branch row x1 (x = act(x1 + irfft)); output
-// rows stored from registers, row stats for InstanceNorm-1.  AH (1 or 2) rows in
-// flight per wave (AH Yn and AH skip slots).  Measured at 721x1440: one row ahead
-// with two 4-wave workgroups per CU beats two rows ahead with one 6-wave one
-// (0.81 vs 0.98 ms): the row FFT itself is VALU/LDS-latency bound, so waves per
-// CU matter more than bytes in flight.
+// rows stored from registers, row stats for InstanceNorm-1.  One row in flight per
+// wave (one Yn and one skip slot).  Measured at 721x1440: one row ahead with two
+// 4-wave workgroups per CU beats two rows ahead with one 6-wave one (0.81 vs
+// 0.98 ms): the row FFT itself is VALU/LDS-latency bound, so waves per CU matter
+// more than bytes in flight.
 // AR: the skip row is read into registers after the FFT instead of an LDS slot
 // (8.8 instead of 14.8 KB of LDS per wave: more waves per CU)
 // SWI_: the FFT codelet's pass-2 swizzle in this inverse kernel too (FixedFFT::SWZ; for
@@ -841,13 +841,15 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
   float2* tw = smem;
   float2* twN = smem + H;
   const int YS = ncy * 1024;
-  static_assert(!AR || (ADD && AH == 1), "register skip rows: one row ahead");
+  // AH: rows in flight per wave
+  static_assert(AH == 1, "only the one-row-ahead form is instantiated");
+  static_assert(!AR || ADD, "register skip rows: with the skip branch only");
   constexpr bool ADMA = ADD && !AR;  // skip row staged by LDS-DMA
-  const int per = RB + AH * YS + (ADMA ? AH * NCA * 1024 : 0);
+  const int per = RB + YS + (ADMA ? NCA * 1024 : 0);
   char* wb = reinterpret_cast<char*>(smem + 2 * H + 2) + (size_t)w * per;
   float2* buf = reinterpret_cast<float2*>(wb);
-  char* yst = wb + RB;                  // AH slots of YS
-  char* ast = wb + RB + AH * YS;        // AH slots of NCA KB
+  char* yst = wb + RB;                  // the Yn slot (YS bytes)
+  char* ast = wb + RB + YS;             // the skip slot (NCA KB)
   for (int t = threadIdx.x; t < H; t += blockDim.x) tw[t] = f.twH[t];
   for (int t = threadIdx.x; t <= H; t += blockDim.x) twN[t] = f.twN[t];
   __syncthreads();
@@ -858,28 +860,24 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
   // page, and no bin k >= mmax is used.  (Clamping to the last chunk wholly inside Yn gave
   // the last row's last bin the value two bins before it.)
   const int64_t yend = ((int64_t)rows * YB - 1) & ~(int64_t)15;
-  auto issue_y = [&](int64_t r, int sl) {
+  auto issue_y = [&](int64_t r) {
     const int64_t a0 = ((int64_t)r * YB) & ~(int64_t)15;
     const char* src = reinterpret_cast<const char*>(in);
-    const uint32_t dst = lds_addr(yst + sl * YS);
+    const uint32_t dst = lds_addr(yst);
     for (int c = 0; c < ncy; ++c)
       glds16(src + min(a0 + c * 1024 + lane * 16, yend), dst + c * 1024);
   };
-  auto issue_a = [&](int64_t r, int sl) {
+  auto issue_a = [&](int64_t r) {
     const char* src = reinterpret_cast<const char*>(addsrc + r * N);
-    const uint32_t dst = lds_addr(ast + sl * NCA * 1024);
+    const uint32_t dst = lds_addr(ast);
 #pragma unroll
     for (int c = 0; c < NCA; ++c)
       glds16(src + min(c * 1024 + lane * 16, RB - 16), dst + c * 1024);
   };
   const int64_t row0 = (int64_t)blockIdx.x * WV + w;
   if (row0 < rows) {
-    issue_y(row0, 0);
-    if constexpr (ADMA) issue_a(row0, 0);
-  }
-  if (AH == 2 && row0 + stride < rows) {
-    issue_y(row0 + stride, 1);
-    if constexpr (ADMA) issue_a(row0 + stride, 1);
+    issue_y(row0);
+    if constexpr (ADMA) issue_a(row0);
   }
   // store instructions per row: the plane path's NST, or one 8-B store per output of the
   // last pass's butterflies (every butterfly iteration has an active lane)
@@ -888,14 +886,10 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
   const int na = ADMA ? NCA : 0;
   int i = 0;
   for (int64_t row = row0; row < rows; row += stride, ++i) {
-    const int sl = AH == 2 ? (i & 1) : 0;
-    const bool e1 = row + stride < rows, e2 = row + 2 * stride < rows;
+    const bool e1 = row + stride < rows;
     // Yn(row) landed: count what this wave issued after it (dma.h)
-    if (AH == 2)
-      wait_vmcnt((i >= 2 ? nst : 0) + na + (i >= 1 ? nst : 0) + (e1 ? ncy + na : 0));
-    else
-      wait_vmcnt(na + (i >= 1 ? nst : 0));
-    const float2* yr = reinterpret_cast<const float2*>(yst + sl * YS) + (((int64_t)row * YB) & 15) / 8;
+    wait_vmcnt(na + (i >= 1 ? nst : 0));
+    const float2* yr = reinterpret_cast<const float2*>(yst) + (((int64_t)row * YB) & 15) / 8;
     // the Hermitian pre-twiddle of bin k, read by the first FFT pass straight from the Yn slot
     auto pre = [&](int k) -> float2 {
       float2 xk = k < mmax ? yr[k] : make_float2(0.f, 0.f);
@@ -917,17 +911,12 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
       float2 skv[AR ? ITL : 1][AR ? RL : 1];
       float2 vo[ITL][RL];
       float s = 0.f;
-      const float2* a2 = reinterpret_cast<const float2*>(ast + sl * NCA * 1024);
+      const float2* a2 = reinterpret_cast<const float2*>(ast);
       float2* x2 = reinterpret_cast<float2*>(x + row * N);
       auto after = [&]() {
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        if (AH == 2 ? e2 : e1) issue_y(row + AH * stride, sl);  // this Yn slot was consumed
-        if constexpr (ADMA) {  // skip row landed (counts as in the plane path below)
-          if (AH == 2)
-            wait_vmcnt((e1 ? ncy + na : 0) + (i >= 1 ? nst : 0) + (e2 ? ncy : 0));
-          else
-            wait_vmcnt(e1 ? ncy : 0);
-        }
+        if (e1) issue_y(row + stride);  // the Yn slot was consumed
+        if constexpr (ADMA) wait_vmcnt(e1 ? ncy : 0);  // skip row landed (as in the plane path below)
         if constexpr (AR) {
           const float2* g2 = reinterpret_cast<const float2*>(addsrc + row * N);
 #pragma unroll
@@ -971,13 +960,13 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       if constexpr (ADMA) {
-        if (AH == 2 ? e2 : e1) issue_a(row + AH * stride, sl);  // this skip slot was consumed
+        if (e1) issue_a(row + stride);  // the skip slot was consumed
       }
       continue;
     }
     CL::template run_loaded<true>(buf, tw, lane, pre, [&]() {
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      if (AH == 2 ? e2 : e1) issue_y(row + AH * stride, sl);  // this Yn slot was consumed
+      if (e1) issue_y(row + stride);  // the Yn slot was consumed
     });
     constexpr int NA4 = (N / 4 + 63) / 64;  // skip-row float4 per lane
     float4 areg[AR ? NA4 : 1];
@@ -989,13 +978,8 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
         areg[j] = n < N / 4 ? g4[n] : make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
-    if constexpr (ADMA) {  // skip row landed
-      if (AH == 2)
-        wait_vmcnt((e1 ? ncy + na : 0) + (i >= 1 ? nst : 0) + (e2 ? ncy : 0));
-      else
-        wait_vmcnt(e1 ? ncy : 0);
-    }
-    const float4* a4 = reinterpret_cast<const float4*>(ast + sl * NCA * 1024);
+    if constexpr (ADMA) wait_vmcnt(e1 ? ncy : 0);  // skip row landed
+    const float4* a4 = reinterpret_cast<const float4*>(ast);
     float4* x4 = reinterpret_cast<float4*>(x + row * N);
     unsigned short* xq = nullptr;
     int64_t ps = 0;
@@ -1056,7 +1040,7 @@ __global__ __launch_bounds__(64 * WV) void fft_c2r_dma_kernel(const float2* __re
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if constexpr (ADMA) {
-      if (AH == 2 ? e2 : e1) issue_a(row + AH * stride, sl);  // this skip slot was consumed
+      if (e1) issue_a(row + stride);  // the skip slot was consumed
     }
   }
 }

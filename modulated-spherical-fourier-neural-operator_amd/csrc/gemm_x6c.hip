@@ -176,8 +176,6 @@ __global__ void spec_weights_3m_kernel(SpecWeightsX6p a) {
 // forward Legendre GEMM): each thread loads a float4 of Re and of Im for the next
 // k-tile before the current one's MFMAs, and after them forms Re + Im, splits the
 // three into bf16x3 and writes the nine B planes into the LDS stage; only A is DMA'd
-// DBG (diagnostic timing builds, wrong results; none is instantiated): 1 no vmcnt wait
-// for the k-tile DMA, 2 no DMA in the loop at all (stale stages), 4 no MFMAs
 // LAY: bit 1 = B planes read in the tiled layout, bit 2 = planes written tiled
 // NS: LDS stages (2; 3 for the x3h DMA-fed layers: two k-tiles in flight, 144 KB)
 // BM_: tile rows (128, or 64 for grids that would not fill the chip: the 120 x 240
@@ -199,13 +197,14 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   constexpr int A_ALL = NMP * A_PLANE;
   constexpr int STAGE = NMP * (A_PLANE + B_PLANE);      // 72 KB (x6) / 48 KB (x3h)
   constexpr int NSTAGE = NS;
-  static_assert(NS == 2 || (NS == 3 && !BF32 && DBG == 0), "three stages: DMA-fed B only");
+  static_assert(NS == 2 || (NS == 3 && !BF32), "three stages: DMA-fed B only");
+  static_assert(DBG == 0, "DBG: timing builds with wrong results (no DMA wait, no DMA, no MFMAs)");
   constexpr int RING_BYTES = NSTAGE * STAGE * 2;
   constexpr int EPI_BYTES = 32 * WGM * (BN + 8) * 4;
   constexpr int LDS_BYTES = RING_BYTES > EPI_BYTES ? RING_BYTES : EPI_BYTES;
   static_assert(STAGE * 2 == (APC + BPC) * 1024, "stage = A + B pieces of 1 KB");
-  // the x3h engine writes hidden planes in the tiled layout only
-  static_assert(NP == 3 || !PLANES_OUT || (LAY & 2) != 0, "x3h: tiled plane output only");
+  // hidden planes leave in the tiled layout only
+  static_assert(PLANES_OUT == ((LAY & 2) != 0), "plane output is tiled, fp32 row output is not");
   typedef typename SplitEng<NP>::frag Frag;
   __shared__ __attribute__((aligned(16))) char lds_raw[LDS_BYTES];
   unsigned short* const ring = reinterpret_cast<unsigned short*>(lds_raw);
@@ -455,20 +454,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
     //         loads of load_bf, which now go first so their latency has the whole k-tile.
     auto step = [&](int kt, auto more_c) {
       constexpr bool MORE = decltype(more_c)::value;
-      if constexpr ((DBG & 1) == 0)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my DMA of k-tile kt landed
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my DMA of k-tile kt landed
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // everyone's landed; stage (kt + 1) & 1 is free
       const Refill r = refill_of(kt + 1, (kt + 1) & 1);
       if constexpr (BF32 && MORE) load_bf(kt + 1);
       __builtin_amdgcn_s_setprio(1);
-      if constexpr ((DBG & 4) == 0) {
-        mfma_tile(kt & 1, [&](int g) {
-          if constexpr (MORE && (DBG & 2) == 0) refill_after(g, r);
-        });
-      } else if constexpr (MORE && (DBG & 2) == 0) {
-        issue(kt + 1, (kt + 1) & 1);
-      }
+      mfma_tile(kt & 1, [&](int g) {
+        if constexpr (MORE) refill_after(g, r);
+      });
       __builtin_amdgcn_s_setprio(0);
       if constexpr (BF32 && MORE) store_bf(kt + 1, (kt + 1) & 1);
     };
@@ -488,7 +482,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       mul[j] = ls;
-      if constexpr (!PLANES_OUT && (LAY & 2) == 0) {
+      if constexpr (!PLANES_OUT) {
         if (p.colscale) mul[j] *= p.colscale[z * p.cs_b + min(n0 + wn * WN + j * 32 + l32, N - 1)];
       }
     }
@@ -512,7 +506,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   float* lds = reinterpret_cast<float*>(lds_raw);
   GemmParams q{};
   q.vecC = 1;
-  if constexpr (PLANES_OUT && (LAY & 2) != 0) {
+  if constexpr (PLANES_OUT) {
     // tiled planes: every row and column of the tile (pad rows / columns are 0)
     constexpr int CS_LD = BN + 8;
     unsigned short* Yt = p.Y + z * p.y_b + (int64_t)tn * p.kt_out * NMP * B_PLANE;
@@ -542,16 +536,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
         for (int pl = 0; pl < NP; ++pl)
           *reinterpret_cast<uint2*>(d + pl * B_PLANE) = make_uint2(ta[pl], tb[pl]);
       }
-      __syncthreads();
-    }
-  } else if constexpr (PLANES_OUT) {
-#pragma unroll
-    for (int mat = 0; mat < 3; ++mat) {
-      q.Cx = p.Y + mat * p.y_mat;
-      q.sC = p.y_b;
-      q.sCxp = p.y_plane;
-      gemm_epilogue<BM, BN, EPI_PLANES, WGM, WGN, MT, NT, 32, floatx16, false>(
-          q, acc[mat], lds, nullptr, nullptr, nullptr, p.co, N, p.ldy, m0, n0);
       __syncthreads();
     }
   } else {

@@ -108,7 +108,7 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
                      const float* addend, int64_t add_bstride, float* out, int B, int64_t P,
                      void* ws, size_t ws_bytes, hipStream_t s, void* cache = nullptr,
                      int cache_valid = 0);
-// inner skip at C = 256 on the mlp_fused_h tiling (x3h): out = Ws·x + bs, x scaled by the
+// skip_h.hip: inner skip at C = 256 on the mlp_fused_h tiling (x3h): out = Ws·x + bs, x scaled by the
 // power-of-two channel scales xs (|xs x| < 2^14), or per pixel in-kernel when xs is null;
 // ws >= skip_h_workspace(B)
 bool skip_h_env();

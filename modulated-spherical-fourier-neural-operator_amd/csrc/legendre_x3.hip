@@ -24,7 +24,6 @@
 // to 32, zero padded), so its staging is plain 16-B copies.
 #include <cstdint>
 #include <cstdio>
-#include <type_traits>
 
 #include "dma.h"
 #include "gemm_common.h"
@@ -101,9 +100,8 @@ constexpr int WGM = 2, WGN = 2, WM = BM / WGM, MT = WM / 32;
 
 __device__ __forceinline__ int swz(int row) { return (row >> 3) & 1; }
 
-// BN: columns per tile; PF: k-tiles in flight in registers; DBG: diagnostic timing
-// builds with wrong results (1 no MFMAs, 4 no main-loop loads).  Only <64, 1> is
-// instantiated: 128 / 192 columns, PF = 2 and the diagnostic builds measured no faster
+// BN: columns per tile.  Only <X3D_BN, 1> is instantiated: 128 / 192 columns, a second
+// k-tile of register prefetch and the diagnostic timing builds measured no faster
 // 
 //
 // Row scales per k-tile: the 8 threads that stage one row's 32 k of a k-tile reduce
@@ -113,6 +111,9 @@ __device__ __forceinline__ int swz(int row) { return (row >> 3) & 1; }
 // per workgroup cost 0.13 / 0.18 ms of the forward / inverse 0.39 / 0.57).
 template <int BN, int PF, int DBG = 0>
 __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
+  static_assert(BN == X3D_BN, "only the X3D_BN-column tile is instantiated");
+  static_assert(PF == 1 && DBG == 0,
+                "PF: k-tiles prefetched in registers; DBG: timing builds with wrong results");
   constexpr int B_PL = KS * BN * 16;
   constexpr int STAGE = 2 * A_PL + 2 * B_PL;  // fp16 per stage
   constexpr int WN = BN / WGN, NT = WN / 32;
@@ -151,14 +152,10 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
   // A: 128 rows x 32 k = 1024 float4, 4 per thread (thread -> row idx / 8, k 4 (idx % 8):
   // the 8 lanes of a row are adjacent); (rows padded to 4 floats and segments to 16: a
   // float4 at k % 4 == 0 stays in its row and block; elements past K are masked)
-  float4 ra[PF][4];
-  uint4 rb[PF][NB];
+  float4 ra[4];
+  uint4 rb[NB];
   const int Kc = K > 0 ? K - 1 : 0;
-  auto load = [&](int kt, auto buf_c) {
-    constexpr int BUF = decltype(buf_c)::value;
-    if constexpr ((DBG & 4) != 0) {
-      if (kt > 1) return;
-    }
+  auto load = [&](int kt) {
     const int k0 = kt * BK;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -166,18 +163,17 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
       const int row = min(m0 + (idx >> 3), M - 1);
       const int k = k0 + 4 * (idx & 7);
       const float* a = A + (int64_t)row * lda;
-      ra[BUF][q] = *reinterpret_cast<const float4*>(a + seg_k(min(k, Kc & ~3), p.segA_w, p.segA_stride));
+      ra[q] = *reinterpret_cast<const float4*>(a + seg_k(min(k, Kc & ~3), p.segA_w, p.segA_stride));
     }
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
       const int idx = tid + 256 * q;
       const int pl = idx / (4 * BN), n = (idx >> 2) % BN, c = idx & 3;
       const int ng = min(n0 + n, N - 1);
-      rb[BUF][q] = *reinterpret_cast<const uint4*>(Bimg + ((int64_t)pl * N + ng) * Kp + k0 + 8 * c);
+      rb[q] = *reinterpret_cast<const uint4*>(Bimg + ((int64_t)pl * N + ng) * Kp + k0 + 8 * c);
     }
   };
-  auto store = [&](int st, int kt, auto buf_c) {
-    constexpr int BUF = decltype(buf_c)::value;
+  auto store = [&](int st, int kt) {
     unsigned short* base = ring + st * STAGE;
     const int k0 = kt * BK;
 #pragma unroll
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
       const int idx = tid + 256 * q;
       const int r = idx >> 3, kk = 4 * (idx & 7);  // k within the tile: 0..28
       const bool rok = m0 + r < M;
-      float v[4] = {ra[BUF][q].x, ra[BUF][q].y, ra[BUF][q].z, ra[BUF][q].w};
+      float v[4] = {ra[q].x, ra[q].y, ra[q].z, ra[q].w};
       float mx = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -210,7 +206,7 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
       const int idx = tid + 256 * q;
       const int pl = idx / (4 * BN), n = (idx >> 2) % BN, c = idx & 3;
       const int ks = c >> 1, hc = c & 1;
-      uint4 v = rb[BUF][q];
+      uint4 v = rb[q];
       if (n0 + n >= N) v = make_uint4(0, 0, 0, 0);
       *reinterpret_cast<uint4*>(base + 2 * A_PL + pl * B_PL + (ks * BN + n) * 16 + 8 * (hc ^ swz(n))) = v;
     }
@@ -256,10 +252,6 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
-          if constexpr ((DBG & 1) != 0) {
-            t[i][j][0] += (float)a[i][0][0] + (float)a[i][1][0] + (float)b[j][0][0] + (float)b[j][1][0];
-            continue;
-          }
           SplitEng<2>::mma(a[i], b[j], t[i][j]);
         }
     }
@@ -278,36 +270,14 @@ __global__ __launch_bounds__(256) void legendre_x3_kernel(X3DParams p) {
     }
   };
 
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  if (nk > 0) load(0, I0{});
-  if constexpr (PF == 2) {
-    if (nk > 1) load(1, I1{});
-  }
-  if (nk > 0) store(0, 0, I0{});
+  if (nk > 0) load(0);
+  if (nk > 0) store(0, 0);
   __syncthreads();
-  if constexpr (PF == 1) {
-    for (int kt = 0; kt < nk; ++kt) {
-      if (kt + 1 < nk) load(kt + 1, I0{});
-      mfma_tile(kt & 1);
-      if (kt + 1 < nk) store((kt + 1) & 1, kt + 1, I0{});
-      __syncthreads();
-    }
-  } else {
-    // register buffer b holds k-tiles of parity b: tile kt + 1 was loaded an iteration
-    // ago, tile kt + 2 goes into the buffer tile kt left
-    auto iter = [&](int kt, auto buf_c) {
-      constexpr int BUF = decltype(buf_c)::value;
-      using Other = std::integral_constant<int, BUF ^ 1>;
-      if (kt + 2 < nk) load(kt + 2, buf_c);
-      mfma_tile(BUF);
-      if (kt + 1 < nk) store(BUF ^ 1, kt + 1, Other{});
-      __syncthreads();
-    };
-    for (int kt = 0; kt < nk; kt += 2) {
-      iter(kt, I0{});
-      if (kt + 1 < nk) iter(kt + 1, I1{});
-    }
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) load(kt + 1);
+    mfma_tile(kt & 1);
+    if (kt + 1 < nk) store((kt + 1) & 1, kt + 1);
+    __syncthreads();
   }
 
   // ---- 1 / tau_n, then the shared fp32 epilogue ---------------------------------------

@@ -1,6 +1,6 @@
 """The MFMA kernels that refill an LDS ring by LDS-DMA while they compute
 (csrc/gemm_x6c.hip: the spectral-MLP layers; csrc/mlp_fused_h.hip: the fused block
-MLP and the two inner-skip kernels).  The spectral layers and the persistent skip issue
+MLP; csrc/skip_h.hip: the two inner-skip kernels).  The spectral layers and the persistent skip issue
 a refill piece by piece between the MFMA groups of a step, the block MLP and the
 one-tile skip as one burst behind the step's first MFMAs; either way what orders a piece
 against the reads of its ring slot is a counted s_waitcnt and a barrier, so a miscount

@@ -1,9 +1,9 @@
 """csrc/mlp_fused_h.hip is built without packed FP32 (csrc/Makefile NOPK_SRCS) for the block
 MLP's sake: its GELU and scale folds run beside the MFMAs, where the packed forms cost more
-than the scalar ones they replace (profiles/r11_mlp_io).  The two inner-skip
-kernels of the same unit keep packed FP32 through a target attribute, because they
-measured slower without.  Both halves are silent if lost (a Makefile word, an attribute
-the compiler may ignore), so this checks the built library: no v_pk_{add,mul,fma}_f32 in
+than the scalar ones they replace (profiles/r11_mlp_io).  The inner-skip
+kernels live in a unit of their own, csrc/skip_h.hip, which is not in NOPK_SRCS and so keeps
+packed FP32, because they measured slower without.  Both halves are one Makefile word
+each and silent if lost, so this checks the built library: no v_pk_{add,mul,fma}_f32 in
 any mlp_fused_h_kernel, some in skip_hp_kernel and skip_h_kernel.  CPU only: disassembles
 the fat binary's gfx950 code objects."""
 import os
@@ -24,8 +24,8 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 @pytest.fixture(scope="module")
 def packed_ops():
-    """{mangled kernel symbol: number of packed-FP32 instructions} of the mlp_fused_h.hip
-    kernels in libmsfno.so"""
+    """{mangled kernel symbol: number of packed-FP32 instructions} of the block-MLP
+    (mlp_fused_h.hip) and inner-skip (skip_h.hip) kernels in libmsfno.so"""
     if not os.path.exists(OBJDUMP):
         pytest.skip("llvm-objdump not available")
     import isa_audit as A

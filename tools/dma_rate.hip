@@ -1,7 +1,7 @@
 // LDS-DMA throughput probe (gfx950): how many bytes per clock can a CU move by
 // global_load_lds_dwordx4 into a ring of LDS slots, from an L2-resident image and from
 // HBM, compared with plain 16-B loads into registers?  The inner-skip kernel streams a
-// 16-KB weight slice (L2) and an 8-KB x piece (HBM) per slice step (mlp_fused_h.hip,
+// 16-KB weight slice (L2) and an 8-KB x piece (HBM) per slice step (skip_h.hip,
 // skip_hp_kernel); this measures the copy engine without the MFMAs.
 // Build: hipcc --offload-arch=gfx950 -O3 tools/dma_rate.hip -o tools/bin/dma_rate
 // Run:   tools/bin/dma_rate   (prints one line per mode: GB/s chip-wide)
