@@ -212,6 +212,27 @@ bool spec_use_x3h() {
   return on && spec_use_3m();
 }
 
+// The x3h chain carries its hidden activations as two fp16 terms under fixed scales: layer
+// l's output is multiplied by sigma_l = 2^-ceil(log2 nu_l), nu_l the largest row sum of
+// |Wr| + |Wi| (spec_scales_x3h_kernel), so that no input bounded by 2^14 overflows.  The
+// values a layer really produces are smaller than that bound by nu_l over the layer's
+// gain, about 1.3 sqrt(ci) for weights without structure, whatever their scale: with the
+// rounding of sigma_l to a power of two, log2(ci) / 2 + 1 bits per hidden layer.  fp16
+// holds 2^14 down to the low term's floor of 2^-25, 39 bits, of which a product wants 22:
+// 17 bits of headroom.  Measured (DESIGN.md §2, 13 x 26, unit-gain weights): the chain stays
+// within 2 x the fp32 oracle's error up to 13.5 bits, 2.5 to 3 x at 17 and 17.5 bits, 50 x
+// and more from 20 bits (hidden 32 at six layers, hidden 128 at five).  Chains that would
+// drain more than X3H_RANGE_BITS take the x6 engine's 3M chain (bf16 planes: fp32's
+// exponent), as MSFNO_SPEC_X3H=0 does for every chain.  The flagship's three layers of 256 ->
+// 512 -> 512 drain 16 bits.
+constexpr float X3H_RANGE_BITS = 16.5f;
+
+static bool spec_x3h_range_ok(int64_t C, int64_t Hs, int nl) {
+  float bits = 0.f;
+  for (int l = 0; l < nl; ++l) bits += 0.5f * std::log2((float)(l == 0 ? C : Hs)) + 1.f;
+  return bits <= X3H_RANGE_BITS;
+}
+
 // floats to reserve for one spectral-MLP hidden buffer (B, 2 Hs, T): fp32, or
 // bf16x3 planes with a row stride padded to 8 on the x6 engine
 int64_t spec_hidden_floats(int B, int64_t Hs, const SpecLayout& L) {
@@ -301,7 +322,7 @@ int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s*
         sw.out[l] = static_cast<unsigned short*>(b.dw.spec[l]);
       }
       spec_weights_3m_layout(sw);
-      if (spec_use_x3h() && b.cs && L.ldT % 4 == 0) {
+      if (spec_use_x3h() && spec_x3h_range_ok(C, Hs, nl) && b.cs && L.ldT % 4 == 0) {
         // x3h engine: two fp16 planes per value, three MFMAs per product; the layer
         // scales (2 floats per layer) live behind layer 0's A image (inside wcache when
         // the images are cached), the per-column input scales in b.cs

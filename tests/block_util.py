@@ -30,9 +30,12 @@ def make_block(meta, params=None):
     norm = partial(torch.nn.InstanceNorm2d, num_features=C, eps=1e-6, affine=True,
                    track_running_stats=False)
     cls = FourierNeuralOperatorBlock_Filmed if meta["filmed"] else FourierNeuralOperatorBlock
-    blk = cls(sht, isht, C, filter_type=meta["filter"], mlp_ratio=2.0, norm_layer=(norm, norm),
-              inner_skip=inner, outer_skip=outer,
-              mlp_mode="distributed" if has_mlp else "none", spectral_layers=3,
+    # optional: the fixtures all have mlp_ratio 2.0 (spectral and MLP hidden width 2 C) and
+    # three spectral layers
+    blk = cls(sht, isht, C, filter_type=meta["filter"], mlp_ratio=meta.get("mlp_ratio", 2.0),
+              norm_layer=(norm, norm), inner_skip=inner, outer_skip=outer,
+              mlp_mode="distributed" if has_mlp else "none",
+              spectral_layers=meta.get("spectral_layers", 3),
               complex_activation="real", use_complex_kernels=True)
     if params is not None:
         missing, unexpected = blk.load_state_dict(params, strict=False)

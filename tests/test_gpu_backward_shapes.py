@@ -261,6 +261,20 @@ BLOCK_CASES = {
 }
 WIDE_NL = "wide_nl_C72_two_ragged_tiles_ksplit4_cswap_across_chunk"
 
+# the spectral MLP off its usual build (three layers, hidden 2 C; the forward's sweep is
+# test_gpu_spectral_mlp.py): carve_* of csrc/block_bwd.cpp size r.h[l] by the layer count and
+# the per-layer loops take ci and co from the hidden width.  13 x 26, lmax 12, C 24, B 2
+SMALL = dict(nlat=13, nlon=26, lmax=12, mmax=13, grid="equiangular", C=24, B=2,
+             filter="non-linear")
+BLOCK_CASES.update({
+    # one layer: the output layer's gradient reads layer 0's activation, r.h has one entry
+    "spec_L1_C24_hidden48": dict(SMALL, spectral_layers=1, mlp_ratio=2.0),
+    # four layers of hidden 36 (no multiple of 16 or 32): three square hidden layers
+    "spec_L4_C24_hidden36": dict(SMALL, spectral_layers=4, mlp_ratio=1.5),
+    # hidden 12 < C: the forward's real-ified 4M chain; block MLP hidden 12 as well
+    "spec_L2_C24_hidden12": dict(SMALL, spectral_layers=2, mlp_ratio=0.5),
+})
+
 
 def _recipe_params(blk, meta):
     """Every parameter of the block from the committed recipe (golden_util.param_recipe /
@@ -326,7 +340,15 @@ def _block_case(name, guard_ws=False):
         guard_intact(ws, nbytes)
     inner, outer, has_mlp = wiring_cfg(meta)
     cfg = sfno_ref.BlockCfg(filter_type=meta["filter"], inner_skip=inner, outer_skip=outer,
-                            has_mlp=has_mlp)
+                            has_mlp=has_mlp, spectral_layers=meta.get("spectral_layers", 3))
+    if "spectral_layers" in meta:
+        # the block was built at the depth and widths the oracle's own recipe gives them
+        shapes = sfno_ref.make_block_params(C, meta["lmax"], meta["mmax"], cfg,
+                                            hidden_factor=meta["mlp_ratio"])
+        assert {k: tuple(v.shape) for k, v in shapes.items()} == \
+            {k: tuple(params[k].shape) for k in shapes}
+        assert len(blk.filter_layer.filter.w) == cfg.spectral_layers
+        assert blk.filter_layer.filter.hidden_size == int(meta["mlp_ratio"] * C)
     pd = {k: (v.double().requires_grad_() if v.is_floating_point() else v)
           for k, v in params.items()}
     sht, isht = _oracle_transforms(meta)
@@ -349,7 +371,14 @@ def _block_case(name, guard_ws=False):
         assert p.grad is not None and torch.isfinite(p.grad).all(), k
     n = _compare_params(tag, named, lambda k: pd[k].grad if pd[k].grad is not None
                         else torch.zeros_like(pd[k]))
-    assert n >= (11 if meta["filter"] == "linear" else 14)
+    if meta["filter"] == "linear":
+        assert n >= 11
+    elif "spectral_layers" in meta:
+        # norm0, norm1, inner skip, fc1, fc2: weight and bias each; layers + 1 spectral
+        # weights (ComplexReLU(real) keeps its bias as a buffer)
+        assert n == 10 + cfg.spectral_layers + 1, n
+    else:
+        assert n >= 14
 
 
 @pytest.mark.parametrize("name", list(BLOCK_CASES))
