@@ -121,6 +121,16 @@ int launch_skip_h(const float* W, const float* xs, const float* x, float* out, c
 // xs[r] = the power of two 2^(14 - e) with max_p |x[r][p]| = f 2^e (rows of P values): the
 // x3h B-row scales of a 1x1 conv whose input carries no norm statistics
 int launch_chan_pow2_scale(const float* x, int64_t rows, int64_t P, float* xs, hipStream_t s);
+// The x3h MLPs' weight preparation (mlp_gen_h.hip; the block MLP's image build uses it too),
+// one 256-thread workgroup per row.  eta[j] = 2^-ceil(log2 L_j), L_j = max(||W1_j||_1,
+// |b1_j|) for the H rows of W1 (H x Ct; b1 or null)
+int launch_x3h_eta(const float* W1, const float* b1, int H, int Ct, float* eta, hipStream_t s);
+// Row scales 2^(15 - e), max |row| = f 2^e, of W1 (H x Ct) and of W2' = W2 diag(1 / eta)
+// (Cout x H): the scales into s1 [H] / s2 [rows2] (both or neither; null: not stored), their
+// inverses into is1 / is2; rows Cout .. rows2 - 1 of s2 / is2 are 0
+int launch_x3h_row_scales(const float* W1, const float* W2, const float* eta, int H, int Ct,
+                          int Cout, int rows2, float* s1, float* s2, float* is1, float* is2,
+                          hipStream_t s);
 size_t mlp_fused_h_image_bytes();
 int launch_mlp_fused_h_images(const float* W1, const float* b1, const float* W2,
                               unsigned short* img, hipStream_t s);

@@ -8,7 +8,8 @@
 //   a·b ~= a1·b0 + a0·b1 + a0·b0     (three fp16 MFMAs, fp32 accumulation; a1·b1 and
 //                                     the representation residuals are O(2^-22))
 //
-// (split_engine.h: split2h, SplitEng<2>; the split of Ootomo & Yokota, "Recovering
+// (split_engine.h: split2h, SplitEng<2>; x3h_tile.h: the tile layout and the pipeline's
+// steps, shared with mlp_gen_h.hip and skip_h.hip; the split of Ootomo & Yokota, "Recovering
 // single precision accuracy from Tensor Cores while surpassing the FP32 theoretical
 // peak performance", 2022).  Products of
 // fp16 values are exact in fp32, so the only errors beyond an fp32 GEMM's own
@@ -39,9 +40,8 @@
 //   W2(j,oh): out rows 128oh..+127, hidden block j:       [pl 2][ot 8][r 16][32 (perm)]
 // ring of four 16-KB slots; image = 64 slices, then the row scales (inverse) of W1
 // (512) and W2' (256), then eta (512), as fp32.
-#include "dma.h"
-#include "gemm_common.h"
 #include "kernels.h"
+#include "x3h_tile.h"
 
 #include <cstdio>
 #include <vector>
@@ -51,7 +51,7 @@ namespace msfno {
 
 namespace {
 
-// (MH_C, MH_PLANE, MH_SLICE, MH_NS: split_engine.h, shared with skip_h.hip)
+// (MH_C, MH_PLANE, MH_SLICE, MH_NS: x3h_tile.h, shared with skip_h.hip)
 constexpr int MH_H = 512;
 constexpr int MH_WAVES = 4;
 constexpr int MH_HB = MH_H / 32;                    // hidden blocks
@@ -77,42 +77,11 @@ struct MlpHParams {
   uint64_t* trace;      // MSFNO_MH_TRACE: 5 words per workgroup, or null
 };
 
-// eta_j = 2^-ceil(log2 L_j), L_j = max(||W1_j||_1, |b1_j|): L_j eta_j <= 1
-__global__ void mh_eta_kernel(const float* __restrict__ W1, const float* __restrict__ b1,
-                              float* __restrict__ eta) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= MH_H) return;
-  const float* row = W1 + (int64_t)r * MH_C;
-  double l1 = 0.0;
-  for (int k = 0; k < MH_C; ++k) l1 += fabs((double)row[k]);
-  const double L = fmax(l1, b1 ? fabs((double)b1[r]) : 0.0) * (1.0 + 1e-6);
-  float e = 1.f;
-  if (L > 0.0 && L < 1e30) {
-    int x;
-    frexp(L, &x);  // L = f 2^x, f in [0.5, 1): L 2^-x < 1
-    e = (float)ldexp(1.0, min(max(-x, -120), 120));
-  }
-  eta[r] = e;
-}
-
-// row scales: 2^(15 - e) with max |row| = f 2^e, f in [0.5, 1) -> max scaled in [2^14, 2^15);
-// the W2 rows taken as W2' = W2 diag(1 / eta)
-__global__ void mh_scale_kernel(const float* __restrict__ W1, const float* __restrict__ W2,
-                                const float* __restrict__ eta, float* __restrict__ s1,
-                                float* __restrict__ s2) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= MH_H + MH_C) return;
-  const bool first = r < MH_H;
-  const float* row = first ? W1 + (int64_t)r * MH_C : W2 + (int64_t)(r - MH_H) * MH_H;
-  const int n = first ? MH_C : MH_H;
-  float m = 0.f;
-  for (int k = 0; k < n; ++k) m = fmaxf(m, fabsf(first ? row[k] : row[k] / eta[k]));
-  const float sc = row_scale(m, 15);
-  if (first) s1[r] = sc; else s2[r - MH_H] = sc;
-}
-
-// W1 (H x C fp32) · diag(s1) -> [j][kh][pl][ks][t][r][32]
-__global__ void mh_w1_image_kernel(const float* __restrict__ W1, const float* __restrict__ s1,
+// (eta_j and the row scales: launch_x3h_eta, launch_x3h_row_scales of mlp_gen_h.hip.  The image
+// keeps only the inverse scales, so the writers below take those: 1 / (1 / s) = s, the
+// scales being powers of two)
+// W1 (H x C fp32) · diag(s1) -> [j][kh][pl][ks][t][r][32]; one thread per pair of columns
+__global__ void mh_w1_image_kernel(const float* __restrict__ W1, const float* __restrict__ is1,
                                    unsigned short* __restrict__ img) {
   constexpr int64_t PAIRS = (int64_t)MH_HB * 2 * 4 * 2 * 16 * 16;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < PAIRS;
@@ -123,25 +92,22 @@ __global__ void mh_w1_image_kernel(const float* __restrict__ W1, const float* __
     const int ks = (int)((e >> 9) & 3);
     const int kh = (int)((e >> 11) & 1);
     const int j = (int)(e >> 12);
-    const int kk = 2 * kkp;
-    const int g = (kk >> 3) ^ mlph_swz(r);
-    const int k = 128 * kh + 32 * ks + 8 * g + (kk & 7);
     const int row = 32 * j + 16 * t + r;
-    const float* src = W1 + (int64_t)row * MH_C + k;
-    const float sc = s1[row];
+    const float* src = W1 + (int64_t)row * MH_C + 128 * kh + 32 * ks + 2 * kkp;
+    const float sc = 1.f / is1[row];
     uint32_t t0, t1;
     split2h(src[0] * sc, src[1] * sc, t0, t1);
     uint32_t* o = reinterpret_cast<uint32_t*>(
-        img + (int64_t)(j * 2 + kh) * MH_SLICE + ((ks * 2 + t) * 16 + r) * 32 + kk);
+        img + (int64_t)(j * 2 + kh) * MH_SLICE + x3h_w1_slice_pos(ks, t, r, 2 * kkp));
     o[0] = t0;
     o[MH_PLANE / 2] = t1;
   }
 }
 
 // W2' (C x H fp32, W2 diag(1 / eta)) · row scales -> [j][oh][pl][ot][r][32], hidden index
-// permuted by mlph_perm
+// permuted by mlph_perm; one thread per pair of k positions kap, kap + 1
 __global__ void mh_w2_image_kernel(const float* __restrict__ W2, const float* __restrict__ eta,
-                                   const float* __restrict__ s2, unsigned short* __restrict__ img) {
+                                   const float* __restrict__ is2, unsigned short* __restrict__ img) {
   constexpr int64_t PAIRS = (int64_t)MH_HB * 2 * 8 * 16 * 16;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < PAIRS;
        e += (int64_t)gridDim.x * blockDim.x) {
@@ -150,26 +116,19 @@ __global__ void mh_w2_image_kernel(const float* __restrict__ W2, const float* __
     const int ot = (int)((e >> 8) & 7);
     const int oh = (int)((e >> 11) & 1);
     const int j = (int)(e >> 12);
-    const int kk = 2 * kkp;
-    const int kap = 8 * ((kk >> 3) ^ mlph_swz(r)) + (kk & 7);
+    const int kap = 2 * kkp;
     const int orow = 128 * oh + 16 * ot + r;
     const float* row = W2 + (int64_t)orow * MH_H + 32 * j;
     const float* er = eta + 32 * j;
-    const float sc = s2[orow];
+    const float sc = 1.f / is2[orow];
     const int k0 = mlph_perm(kap), k1 = mlph_perm(kap + 1);
     uint32_t t0, t1;
     split2h(row[k0] / er[k0] * sc, row[k1] / er[k1] * sc, t0, t1);
     uint32_t* o = reinterpret_cast<uint32_t*>(
-        img + (int64_t)(j * 2 + oh) * MH_SLICE + (ot * 16 + r) * 32 + kk);
+        img + (int64_t)(j * 2 + oh) * MH_SLICE + ot * 512 + x3h_tile_pos(r, kap));
     o[0] = t0;
     o[MH_PLANE / 2] = t1;
   }
-}
-
-// 1 / scale, in place
-__global__ void mh_invert_kernel(float* __restrict__ s) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < MH_H + MH_C) s[r] = 1.f / s[r];
 }
 
 __device__ __forceinline__ const unsigned short* mh_slice_src(const MlpHParams& p, int q) {
@@ -218,17 +177,10 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
   const int64_t px = (int64_t)(lin - z * p.tiles_per_field) * TPX + 16 * wave + r16;
 
   // ---- slices 0..NS-1 in flight --------------------------------------------------------
-  const uint32_t ring_lds = lds_addr(ring);
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  uint32_t piece_off[4];
+  const X3hRing<W, NS> wring(ring, wave, lane);
+  auto slice = [&](int q) { return mh_slice_src(p, q); };
 #pragma unroll
-  for (int i = 0; i < 4; ++i) piece_off[i] = (uint32_t)(i * W * 1024 + lane * 16);
-  auto issue = [&](int q) {
-    const uint64_t src = reinterpret_cast<uint64_t>(mh_slice_src(p, q)) + (uint64_t)wave_u * 1024;
-    glds16x4<W * 1024>(src, piece_off, ring_lds + (uint32_t)((q % NS) * MH_SLICE * 2 + wave_u * 1024));
-  };
-#pragma unroll
-  for (int q = 0; q < NS; ++q) issue(q);
+  for (int q = 0; q < NS; ++q) wring.fill(q, slice(q));
 
   // ---- x1 loads, the field's bound B_b = max_c abound (thread tid: channel tid) ------
   const int64_t pxc = px < P ? px : P - 1;
@@ -255,8 +207,8 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
   if (lane == 0) red[wave] = bm;
   __syncthreads();  // (also: the first NS slices and the x1 loads landed)
   const float Bb = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float xi = pow2_below(Bb, 14, 120);          // |x^ xi| < 2^14
-  const float etab = pow2_below(Bb + 1.f, 14, 120);  // |h eta_j eta_b| < 2^14
+  const X3hRange rg = x3h_range(Bb);  // |x^ xi| < 2^14, |h eta_j eta_b| < 2^14
+  const float xi = rg.xi, etab = rg.eta;
 
   // ---- normalised x1 -> fp16x2 B fragments (k-step ks: channels 32 ks + 8 g + 0..7) ----
   const float* sc = p.scale + (int64_t)z * MH_C;
@@ -273,18 +225,12 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
                          sb.x * xi, sb.y * xi, sb.z * xi, sb.w * xi};
     const float tv[8] = {ta.x * xi, ta.y * xi, ta.z * xi, ta.w * xi,
                          tb.x * xi, tb.y * xi, tb.z * xi, tb.w * xi};
-    uint32_t t[2][4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      split2h(fmaf(sv[2 * e], xv[ks][2 * e], tv[2 * e]),
-              fmaf(sv[2 * e + 1], xv[ks][2 * e + 1], tv[2 * e + 1]), t[0][e], t[1][e]);
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+    x3h_split8([&](int e) { return fmaf(sv[e], xv[ks][e], tv[e]); }, xf[ks]);
   }
   floatx4 oacc[16];
 #pragma unroll
   for (int ot = 0; ot < 16; ++ot) oacc[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const float ixi = 1.f / xi, ietab = 1.f / etab;
+  const float ixi = rg.ixi, ietab = rg.ieta;
   for (int i = tid; i < MH_H; i += 64 * W) {
     b1s[i] = p.b1[i];
     is1s[i] = p.inv_s1[i] * ixi;
@@ -305,28 +251,18 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     for (int t = 0; t < 2; ++t) hacc[a][t] = floatx4{0.f, 0.f, 0.f, 0.f};
   uint32_t hfu[2][4];  // fc2 B fragment of the converted block [plane][pair]
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
+  const int a_lane = x3h_a_lane(r16, g);
   auto afrag = [&](const unsigned short* q) -> half8 {
     return *reinterpret_cast<const half8*>(q);
   };
 
   // step q: slice q landed for every wave (slices up to q + NS - 2 may stay in flight);
   // the slot of slice q - 1 is free and takes slice q + NS - 1
-  auto step_begin = [&](int q) {
-    const int after = min(NS - 2, MH_NSLICE - 1 - q);
-    if (after >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    return ring + (q % NS) * MH_SLICE;
-  };
+  auto step_begin = [&](int q) { return wring.landed(q, MH_NSLICE); };
   // (the refill stays one burst after the step's first MFMAs: spread over the step as four
   // single pieces it measured 1.964 against 1.970 ms in-block, inside the run-to-run
   // spread, profiles/r09_refill/ab4_table.txt)
-  auto refill = [&](int q) {
-    if (q >= 1 && q + NS - 1 < MH_NSLICE) issue(q + NS - 1);
-  };
+  auto refill = [&](int q) { wring.refill(q, MH_NSLICE, slice); };
 
   // two tiles' products interleaved (no MFMA reads the accumulator its predecessor writes;
   // each accumulator sees the same three products in the same order as SplitEng<2>::mma)
@@ -351,17 +287,13 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     const float2 b = *reinterpret_cast<const float2*>(b1s + row);
     const float2 is = *reinterpret_cast<const float2*>(is1s + row);
     const float2 hs = *reinterpret_cast<const float2*>(hss + row);
-    f32x2 v = {fmaf(hacc[PAR][t][i], is.x, b.x), fmaf(hacc[PAR][t][i + 1], is.y, b.y)};
-    v = gelu_erf2(v) * f32x2{hs.x, hs.y};
-    split2h(v.x, v.y, hfu[0][e2], hfu[1][e2]);
+    x3h_hidden_pair(hacc[PAR][t][i], hacc[PAR][t][i + 1], is, 1.f, b, hs, 1.f, hfu[0][e2], hfu[1][e2]);
   };
 
-  auto fc1_step = [&](const unsigned short* slot, int q, auto kh_c, auto par_c, auto conv_c,
-                      int jc) {
-    constexpr int KH = decltype(kh_c)::value, PAR = decltype(par_c)::value;
-    constexpr bool CONV = decltype(conv_c)::value;
-    using PPrev = std::integral_constant<int, PAR ^ 1>;
-    auto aoff = [&](int u, int pl) { return ((pl * 4 + (u >> 1)) * 2 + (u & 1)) * 512 + a_lane; };
+  // One slice step: the slot's eight A tiles (both planes of tile u at aoff(u, pl)), read
+  // AHEAD ahead of their MFMAs, each times the B operand bf(u) into acc(u); the refill
+  // behind tile 0's products, after(u) behind tile u's (ILV: behind the pair u, u + 1)
+  auto walk = [&](const unsigned short* slot, int q, auto aoff, auto bf, auto acc, auto after) {
     half8 a[AHEAD + 2][2];  // (the pair path rotates over AHEAD + 2)
 #pragma unroll
     for (int k = 0; k < AHEAD; ++k)
@@ -370,8 +302,7 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
     if constexpr (ilv) {  // tile pairs (u, u + 1): A fragments AHEAD = 2 ahead cover both
 #pragma unroll
       for (int u = 0; u < 8; u += 2) {
-        mfma3x2(a[u % (AHEAD + 2)], xf[KH * 4 + (u >> 1)], hacc[PAR][0],
-                a[(u + 1) % (AHEAD + 2)], xf[KH * 4 + (u >> 1)], hacc[PAR][1]);
+        mfma3x2(a[u % (AHEAD + 2)], bf(u), acc(u), a[(u + 1) % (AHEAD + 2)], bf(u + 1), acc(u + 1));
 #pragma unroll
         for (int k = 0; k < 2; ++k)
           if (u + k + AHEAD < 8) {
@@ -380,25 +311,36 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
               a[(u + k + AHEAD) % (AHEAD + 2)][pl] = afrag(slot + aoff(u + k + AHEAD, pl));
           }
         if (u == 0) refill(q);
-        if constexpr (CONV) {
-          if (u == 2 || u == 6) conv_pair(jc, 2 * KH + (u >> 2), PPrev{});
-        }
+        after(u);
       }
     } else {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (u + AHEAD < 8) {
+      for (int u = 0; u < 8; ++u) {
+        if (u + AHEAD < 8) {
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-          a[(u + AHEAD) % (AHEAD + 1)][pl] = afrag(slot + aoff(u + AHEAD, pl));
-      }
-      SplitEng<2>::mma(a[u % (AHEAD + 1)], xf[KH * 4 + (u >> 1)], hacc[PAR][u & 1]);
-      if (u == 0) refill(q);
-      if constexpr (CONV) {
-        if (u == 2 || u == 6) conv_pair(jc, 2 * KH + (u >> 2), PPrev{});
+          for (int pl = 0; pl < 2; ++pl)
+            a[(u + AHEAD) % (AHEAD + 1)][pl] = afrag(slot + aoff(u + AHEAD, pl));
+        }
+        SplitEng<2>::mma(a[u % (AHEAD + 1)], bf(u), acc(u));
+        if (u == 0) refill(q);
+        after(u);
       }
     }
-    }
+  };
+  auto fc1_step = [&](const unsigned short* slot, int q, auto kh_c, auto par_c, auto conv_c,
+                      int jc) {
+    constexpr int KH = decltype(kh_c)::value, PAR = decltype(par_c)::value;
+    constexpr bool CONV = decltype(conv_c)::value;
+    using PPrev = std::integral_constant<int, PAR ^ 1>;
+    walk(
+        slot, q, [&](int u, int pl) { return ((pl * 4 + (u >> 1)) * 2 + (u & 1)) * 512 + a_lane; },
+        [&](int u) -> const half8(&)[2] { return xf[KH * 4 + (u >> 1)]; },
+        [&](int u) -> floatx4& { return hacc[PAR][u & 1]; },
+        [&](int u) {
+          if constexpr (CONV) {
+            if (u == 2 || u == 6) conv_pair(jc, 2 * KH + (u >> 2), PPrev{});
+          }
+        });
     if constexpr (CONV && KH == 1) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) hacc[PAR ^ 1][t] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -406,39 +348,12 @@ __device__ __forceinline__ void mlp_fused_h_tile(const MlpHParams& p, int lin, c
   };
   auto fc2_step = [&](const unsigned short* slot, int q, auto oh_c) {
     constexpr int OH = decltype(oh_c)::value;
-    auto aoff = [&](int u, int pl) { return (pl * 8 + u) * 512 + a_lane; };
-    const half8 hb[2] = {frag_cast<half8>(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]),
-                         frag_cast<half8>(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3])};
-    half8 a[AHEAD + 2][2];  // (the pair path rotates over AHEAD + 2)
-#pragma unroll
-    for (int k = 0; k < AHEAD; ++k)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) a[k][pl] = afrag(slot + aoff(k, pl));
-    if constexpr (ilv) {
-#pragma unroll
-      for (int u = 0; u < 8; u += 2) {
-        mfma3x2(a[u % (AHEAD + 2)], hb, oacc[OH * 8 + u], a[(u + 1) % (AHEAD + 2)], hb, oacc[OH * 8 + u + 1]);
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-          if (u + k + AHEAD < 8) {
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl)
-              a[(u + k + AHEAD) % (AHEAD + 2)][pl] = afrag(slot + aoff(u + k + AHEAD, pl));
-          }
-        if (u == 0) refill(q);
-      }
-    } else {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (u + AHEAD < 8) {
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-          a[(u + AHEAD) % (AHEAD + 1)][pl] = afrag(slot + aoff(u + AHEAD, pl));
-      }
-      SplitEng<2>::mma(a[u % (AHEAD + 1)], hb, oacc[OH * 8 + u]);
-      if (u == 0) refill(q);
-    }
-    }
+    half8 hb[2];
+    x3h_frags(hfu, hb);
+    walk(
+        slot, q, [&](int u, int pl) { return (pl * 8 + u) * 512 + a_lane; },
+        [&](int) -> const half8(&)[2] { return hb; },
+        [&](int u) -> floatx4& { return oacc[OH * 8 + u]; }, [](int) {});
   };
 
   using I0 = std::integral_constant<int, 0>;
@@ -547,20 +462,16 @@ size_t mlp_fused_h_image_bytes() {
 
 int launch_mlp_fused_h_images(const float* W1, const float* b1, const float* W2,
                               unsigned short* img, hipStream_t s) {
-  float* sc = reinterpret_cast<float*>(img + MH_IMG_ELEMS);
-  float* eta = sc + MH_H + MH_C;
-  hipLaunchKernelGGL(mh_eta_kernel, dim3(MH_H / 256), dim3(256), 0, s, W1, b1, eta);
-  MSFNO_TRY(launch_check("mh_eta"));
-  hipLaunchKernelGGL(mh_scale_kernel, dim3((MH_H + MH_C + 255) / 256), dim3(256), 0, s, W1, W2, eta,
-                     sc, sc + MH_H);
-  MSFNO_TRY(launch_check("mh_scale"));
-  hipLaunchKernelGGL(mh_w1_image_kernel, dim3(256), dim3(256), 0, s, W1, sc, img);
+  float* isc = reinterpret_cast<float*>(img + MH_IMG_ELEMS);  // inverse scales: W1's, then W2's
+  float* eta = isc + MH_H + MH_C;
+  MSFNO_TRY(launch_x3h_eta(W1, b1, MH_H, MH_C, eta, s));
+  MSFNO_TRY(launch_x3h_row_scales(W1, W2, eta, MH_H, MH_C, MH_C, MH_C, nullptr, nullptr, isc,
+                                  isc + MH_H, s));
+  hipLaunchKernelGGL(mh_w1_image_kernel, dim3(256), dim3(256), 0, s, W1, isc, img);
   MSFNO_TRY(launch_check("mh_w1_image"));
-  hipLaunchKernelGGL(mh_w2_image_kernel, dim3(256), dim3(256), 0, s, W2, eta, sc + MH_H,
+  hipLaunchKernelGGL(mh_w2_image_kernel, dim3(256), dim3(256), 0, s, W2, eta, isc + MH_H,
                      img + (int64_t)MH_HB * 2 * MH_SLICE);
-  MSFNO_TRY(launch_check("mh_w2_image"));
-  hipLaunchKernelGGL(mh_invert_kernel, dim3((MH_H + MH_C + 255) / 256), dim3(256), 0, s, sc);
-  return launch_check("mh_invert");
+  return launch_check("mh_w2_image");
 }
 
 int launch_mlp_fused_h(const float* x1, const float* scale, const float* shift,

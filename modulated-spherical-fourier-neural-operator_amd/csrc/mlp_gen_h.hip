@@ -3,8 +3,8 @@
 //   out = W2 · GELU(W1 · [x ; x2] + b1) (+ b2) (+ addend)
 // one launch, the hidden activation on-chip: the tiling of mlp_fused_h_kernel (16 pixels
 // per wave, 64 per workgroup, two workgroups per CU, 16x16x32 fp16 MFMAs, three per fp32
-// product; split_engine.h has the engine, mlp_fused_h.hip its error bound) with
-// compile-time widths:
+// product; split_engine.h has the engine, mlp_fused_h.hip its error bound, x3h_tile.h the
+// steps of the tile pipeline) with compile-time widths:
 // KS k-steps of 32 input channels (Cin + Cin2 <= 32 KS), H hidden rows (runtime, a
 // multiple of 64) and OT output tiles of 16 channels (Cout <= 16 OT).
 //
@@ -30,9 +30,8 @@
 // fc1 tile (ks, t) of block j: W1 rows 32 j + 16 t + r, columns 32 ks + k;
 // fc2 tile ot of block j: W2' rows 16 ot + r, hidden columns 32 j + mlph_perm(k) (the C
 // layout of the fc1 accumulators becomes fc2's B fragment in place).
-#include "dma.h"
-#include "gemm_common.h"
 #include "kernels.h"
+#include "x3h_tile.h"
 
 #include <algorithm>
 #include <mutex>
@@ -48,7 +47,8 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MG_TILE = 1024;   // fp16 per 2-KB tile (two 512-element planes)
 constexpr int MG_SLICE = 8;     // tiles per 16-KB slice
-constexpr int MG_NS = 4;        // ring slots
+constexpr int MG_NS = MH_NS;    // ring slots
+static_assert(MG_SLICE * MG_TILE == MH_SLICE, "the slice of x3h_tile.h");
 constexpr int MG_WAVES = 4;
 constexpr int MG_H_MAX = 256;
 
@@ -72,11 +72,13 @@ __device__ __forceinline__ void mg_for(F&& f) {
 }
 
 // ---- weight image ------------------------------------------------------------------
-// eta_j = 2^-ceil(log2 L_j), L_j = max(||W1_j||_1, |b1_j|); W1 (H x Ct).  One 256-thread
-// workgroup per row (the row sum in fp64, a fixed reduction order)
-__global__ __launch_bounds__(256) void mg_eta_kernel(const float* __restrict__ W1,
-                                                     const float* __restrict__ b1, int Ct,
-                                                     float* __restrict__ eta) {
+// (x3h_eta_kernel and x3h_row_scale_kernel also prepare the block MLP's image,
+// mlp_fused_h.hip, through launch_x3h_eta / launch_x3h_row_scales)
+// eta_j = 2^-ceil(log2 L_j), L_j = max(||W1_j||_1, |b1_j|): L_j eta_j <= 1; W1 (H x Ct).
+// One 256-thread workgroup per row (the row sum in fp64, a fixed reduction order)
+__global__ __launch_bounds__(256) void x3h_eta_kernel(const float* __restrict__ W1,
+                                                      const float* __restrict__ b1, int Ct,
+                                                      float* __restrict__ eta) {
   __shared__ double red[256];
   const int r = blockIdx.x, t = threadIdx.x;
   const float* row = W1 + (int64_t)r * Ct;
@@ -89,47 +91,41 @@ __global__ __launch_bounds__(256) void mg_eta_kernel(const float* __restrict__ W
     __syncthreads();
   }
   if (t != 0) return;
-  const double L = fmax(red[0], fabs((double)b1[r])) * (1.0 + 1e-6);
+  const double L = fmax(red[0], b1 ? fabs((double)b1[r]) : 0.0) * (1.0 + 1e-6);
   float e = 1.f;
   if (L > 0.0 && L < 1e30) {
     int x;
-    frexp(L, &x);
+    frexp(L, &x);  // L = f 2^x, f in [0.5, 1): L 2^-x < 1
     e = (float)ldexp(1.0, min(max(-x, -120), 120));
   }
   eta[r] = e;
 }
 
-// row scales 2^(15 - e), max |row| = f 2^e (W2 rows taken as W2 diag(1 / eta)); inverses
-// into is1 [H] / is2 [16 OT] (0 past Cout).  One 256-thread workgroup per row
-__global__ __launch_bounds__(256) void mg_scale_kernel(
+// row scales 2^(15 - e), max |row| = f 2^e -> the largest scaled entry in [2^14, 2^15) (W2
+// rows taken as W2' = W2 diag(1 / eta)): into s1 [H] / s2 [rows2] when given, inverses into
+// is1 / is2 (0 past Cout).  One 256-thread workgroup per row
+__global__ __launch_bounds__(256) void x3h_row_scale_kernel(
     const float* __restrict__ W1, const float* __restrict__ W2, const float* __restrict__ eta,
     int H, int Ct, int Cout, float* __restrict__ s1, float* __restrict__ s2,
     float* __restrict__ is1, float* __restrict__ is2) {
-  __shared__ float red[256];
+  __shared__ float wmax[4];
   const int r = blockIdx.x, t = threadIdx.x;
   const bool first = r < H;
-  if (!first && r - H >= Cout) {
-    if (t == 0) { s2[r - H] = 0.f; is2[r - H] = 0.f; }
-    return;
-  }
-  const float* row = first ? W1 + (int64_t)r * Ct : W2 + (int64_t)(r - H) * H;
-  const int n = first ? Ct : H;
-  float m = 0.f;
-  for (int k = t; k < n; k += 256) m = fmaxf(m, fabsf(first ? row[k] : row[k] / eta[k]));
-  red[t] = m;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (t < o) red[t] = fmaxf(red[t], red[t + o]);
-    __syncthreads();
+  float sc = 0.f, isc = 0.f;  // a W2 row past Cout
+  if (first || r - H < Cout) {
+    const float* row = first ? W1 + (int64_t)r * Ct : W2 + (int64_t)(r - H) * H;
+    const int n = first ? Ct : H;
+    float m = 0.f;
+    for (int k = t; k < n; k += 256) m = fmaxf(m, fabsf(first ? row[k] : row[k] / eta[k]));
+    sc = row_scale(x3h_block_max(m, wmax), 15);
+    isc = 1.f / sc;
   }
   if (t != 0) return;
-  m = red[0];
-  const float sc = row_scale(m, 15);
-  if (first) { s1[r] = sc; is1[r] = 1.f / sc; }
-  else { s2[r - H] = sc; is2[r - H] = 1.f / sc; }
+  if (s1) (first ? s1[r] : s2[r - H]) = sc;
+  (first ? is1[r] : is2[r - H]) = isc;
 }
 
-// one thread per fp16 pair of a real (non-pad) tile
+// one thread per fp16 pair (columns kap, kap + 1 of row r) of a real (non-pad) tile
 // layout 0: the unit stream above; layout 1 (mlp_gen_hp_kernel): all fc1 tiles first,
 // block-major (tile 2 KS j + i), then the fc2 tiles output-tile-major (tile 2 KS HB +
 // HB ot + j), no pad tiles
@@ -143,10 +139,8 @@ __global__ void mg_image_kernel(const float* __restrict__ W1, const float* __res
        e += (int64_t)gridDim.x * blockDim.x) {
     const bool fc1 = e < n1;
     const int64_t f = fc1 ? e : e - n1;
-    const int kkp = (int)(f & 15), r = (int)((f >> 4) & 15);
+    const int kap = 2 * (int)(f & 15), r = (int)((f >> 4) & 15);
     const int64_t tile_id = f >> 8;
-    const int kk = 2 * kkp;
-    const int kap = 8 * ((kk >> 3) ^ mlph_swz(r)) + (kk & 7);  // k of the stored position kk
     float v0, v1;
     int64_t tile;
     if (fc1) {
@@ -175,7 +169,7 @@ __global__ void mg_image_kernel(const float* __restrict__ W1, const float* __res
     }
     uint32_t t0, t1;
     split2h(v0, v1, t0, t1);
-    uint32_t* o = reinterpret_cast<uint32_t*>(img + tile * MG_TILE + r * 32 + kk);
+    uint32_t* o = reinterpret_cast<uint32_t*>(img + tile * MG_TILE + x3h_tile_pos(r, kap));
     o[0] = t0;
     o[256] = t1;  // plane 1: +512 fp16
   }
@@ -232,18 +226,11 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
   const int H = p.H, HB = H >> 5, nslice = p.nslice;
 
   // ---- slices 0..NS-1 in flight ------------------------------------------------------
-  const uint32_t ring_lds = lds_addr(ring);
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  uint32_t piece_off[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) piece_off[i] = (uint32_t)(i * W * 1024 + lane * 16);
-  auto issue = [&](int q) {
-    const uint64_t src = reinterpret_cast<uint64_t>(p.img + (int64_t)q * SLICE_E) + (uint64_t)wave_u * 1024;
-    glds16x4<W * 1024>(src, piece_off, ring_lds + (uint32_t)((q % NS) * SLICE_E * 2 + wave_u * 1024));
-  };
+  const X3hRing<W, NS> wring(ring, wave, lane);
+  auto slice = [&](int q) { return p.img + (int64_t)q * SLICE_E; };
 #pragma unroll
   for (int q = 0; q < NS; ++q)
-    if (q < nslice) issue(q);
+    if (q < nslice) wring.fill(q, slice(q));
 
   // ---- x of the wave's 16 pixels (k-step ks: channels 32 ks + 8 g + e) -----------------
   const float* xb = p.x + (int64_t)z * p.Cin * P + pxc;
@@ -309,21 +296,11 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
   for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(xv[ks][e]));
-  m = fmaxf(m, __shfl_xor(m, 16));
-  m = fmaxf(m, __shfl_xor(m, 32));
-  const float xi = pow2_below(m, 14, 120);          // |x xi| < 2^14
-  const float etap = pow2_below(m + 1.f, 14, 120);  // |h eta_j etap| < 2^14
-  const float ixi = 1.f / xi, ietap = 1.f / etap;
+  const X3hRange rg = x3h_range(x3h_pixel_max(m));  // |x xi| < 2^14, |h eta_j eta| < 2^14
+  const float xi = rg.xi, etap = rg.eta, ixi = rg.ixi, ietap = rg.ieta;
   half8 xf[KS][2];
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) {
-    uint32_t t[2][4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      split2h(xv[ks][2 * e] * xi, xv[ks][2 * e + 1] * xi, t[0][e], t[1][e]);
-#pragma unroll
-    for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
-  }
+  for (int ks = 0; ks < KS; ++ks) x3h_split8([&](int e) { return xv[ks][e] * xi; }, xf[ks]);
   floatx4 oacc[OT];
 #pragma unroll
   for (int ot = 0; ot < OT; ++ot) oacc[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -365,19 +342,14 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     for (int t = 0; t < 2; ++t) hacc[a][t] = floatx4{0.f, 0.f, 0.f, 0.f};
   uint32_t hfu[2][4];  // fc2 B fragment of the converted block [plane][pair]
   half8 hb[2];
-  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
+  const int a_lane = x3h_a_lane(r16, g);
 
   // slice q landed for every wave (up to NS - 2 later slices stay in flight); the slot of
   // slice q - 1 is free and takes slice q + NS - 1
   auto step_begin = [&](int q) {
-    const int after = min(NS - 2, nslice - 1 - q);
-    if (after >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (q >= 1 && q + NS - 1 < nslice) issue(q + NS - 1);
-    return ring + (q % NS) * SLICE_E;
+    const unsigned short* slot = wring.landed(q, nslice);
+    wring.refill(q, nslice, slice);
+    return slot;
   };
   // pair e2 (0..3) of hidden block j in hacc[PAR]: unscale, + b1, GELU(erf), scale, split
   auto conv_pair = [&](int j, int e2, auto par_c) {
@@ -387,14 +359,9 @@ __global__ __launch_bounds__(256, 2) void mlp_gen_h_kernel(MlpGParams p) {
     const float2 b = *reinterpret_cast<const float2*>(b1s + row);
     const float2 is = *reinterpret_cast<const float2*>(is1s + row);
     const float2 hs = *reinterpret_cast<const float2*>(etas + row);
-    f32x2 v = {fmaf(hacc[PAR][t][i], is.x * ixi, b.x), fmaf(hacc[PAR][t][i + 1], is.y * ixi, b.y)};
-    v = gelu_erf2(v) * f32x2{hs.x * etap, hs.y * etap};
-    split2h(v.x, v.y, hfu[0][e2], hfu[1][e2]);
+    x3h_hidden_pair(hacc[PAR][t][i], hacc[PAR][t][i + 1], is, ixi, b, hs, etap, hfu[0][e2], hfu[1][e2]);
   };
-  auto make_hb = [&]() {
-    hb[0] = frag_cast<half8>(hfu[0][0], hfu[0][1], hfu[0][2], hfu[0][3]);
-    hb[1] = frag_cast<half8>(hfu[1][0], hfu[1][1], hfu[1][2], hfu[1][3]);
-  };
+  auto make_hb = [&]() { x3h_frags(hfu, hb); };
 
   // one unit: FC1 -> fc1 tiles of block j into hacc[PAR] (converting block j - 1 from
   // hacc[PAR ^ 1] on the way when FC2), FC2 -> fc2 tiles of block j - 1
@@ -542,12 +509,6 @@ struct GpShape {
   }
 };
 
-template <int N>
-__device__ __forceinline__ void gp_wait_vm() {
-  static_assert(N >= 0 && N <= 63, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
-}
-
 template <int KS, int OT, bool ADD, int NS_, int PG_>
 __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParams p) {
   using S = GpShape<KS, OT, ADD, NS_, PG_>;
@@ -660,6 +621,14 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
   floatx4 oacc[2][PG];          // fc2 accumulators [output-tile parity][pg]
   float ixi[PG], etap[PG], ietap[PG], iet_prev[PG];
 
+  // pixel group pg's range scalars from the lane's share m of its pixel's bound; returns xi
+  auto set_range = [&](int pg, float m) {
+    const X3hRange rg = x3h_range(x3h_pixel_max(m));
+    etap[pg] = rg.eta;
+    ixi[pg] = rg.ixi;
+    ietap[pg] = rg.ieta;
+    return rg.xi;
+  };
   // x (per pixel: the range scales, then the fp16x2 split); xv[pg][ks][e] raw, 0 past Cin
   auto split_x = [&](const float (&xv)[PG][KS][8]) {
 #pragma unroll
@@ -669,21 +638,9 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
       for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
         for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf(xv[pg][ks][e]));
-      m = fmaxf(m, __shfl_xor(m, 16));
-      m = fmaxf(m, __shfl_xor(m, 32));
-      const float xi = pow2_below(m, 14, 120);
-      etap[pg] = pow2_below(m + 1.f, 14, 120);
-      ixi[pg] = 1.f / xi;
-      ietap[pg] = 1.f / etap[pg];
+      const float xi = set_range(pg, m);
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        uint32_t t[2][4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          split2h(xv[pg][ks][2 * e] * xi, xv[pg][ks][2 * e + 1] * xi, t[0][e], t[1][e]);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
-      }
+      for (int ks = 0; ks < KS; ++ks) x3h_split8([&](int e) { return xv[pg][ks][e] * xi; }, xf[pg][ks]);
     }
   };
 
@@ -717,7 +674,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
       oacc[a][pg] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
+  const int a_lane = x3h_a_lane(r16, g);
   float* const ep = epi_all + wave * 16 * ERS;
   // pair e2 of hidden block j, pixel group pg (hacc[j & 1]): unscale, + b1, GELU, scale, split
   auto conv = [&](auto jc, auto pgc, auto e2c) {
@@ -728,9 +685,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
     const float2 is = *reinterpret_cast<const float2*>(is1s + row);
     const float2 hs = *reinterpret_cast<const float2*>(etas + row);
     const floatx4& h = hacc[j & 1][pg][t];
-    f32x2 v = {fmaf(h[i], is.x * ixi[pg], b.x), fmaf(h[i + 1], is.y * ixi[pg], b.y)};
-    v = gelu_erf2(v) * f32x2{hs.x * etap[pg], hs.y * etap[pg]};
-    split2h(v.x, v.y, hf[j][pg][0][e2], hf[j][pg][1][e2]);
+    x3h_hidden_pair(h[i], h[i + 1], is, ixi[pg], b, hs, etap[pg], hf[j][pg][0][e2], hf[j][pg][1][e2]);
   };
   // the conversions of a block: 4 pairs per pixel group, spread over the next block's tiles
   constexpr int NCONV = 4 * PG;
@@ -743,7 +698,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
   half8 a[NA][2];
   auto prep = [&](auto qc, uint32_t slot_off) {
     constexpr int Q = decltype(qc)::value;
-    gp_wait_vm<S::younger(Q)>();
+    x3h_wait_vm<S::younger(Q)>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const unsigned short* ws = reinterpret_cast<const unsigned short*>(lds + slot_off);
@@ -768,9 +723,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
       e0[2 * ERS] = fmaf(acc[pg][2], is.z * iet[pg], bb.z);
       e0[3 * ERS] = fmaf(acc[pg][3], is.w * iet[pg], bb.w);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    x3h_wave_handover();
   };
   auto epi_store = [&](int ot, const Tile& tw, const char* aslot) {
     // buffer stores: every wave issues all PG (the vmcnt counts stay exact); a lane past
@@ -789,9 +742,7 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
       const uint32_t off = pxl < P ? (uint32_t)(((int64_t)(16 * ot + row) * P + pxl) * 4) : 0x80000000u;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), orsrc, off, 0, 2 /* nt */);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    x3h_wave_handover();
   };
 
   prep(std::integral_constant<int, 0>{}, 0u);
@@ -856,8 +807,8 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
           }
 #pragma unroll
           for (int pg = 0; pg < PG; ++pg) {
-            const half8 hb[2] = {frag_cast<half8>(hf[u][pg][0][0], hf[u][pg][0][1], hf[u][pg][0][2], hf[u][pg][0][3]),
-                                 frag_cast<half8>(hf[u][pg][1][0], hf[u][pg][1][1], hf[u][pg][1][2], hf[u][pg][1][3])};
+            half8 hb[2];
+            x3h_frags(hf[u][pg], hb);
             SplitEng<2>::mma(av, hb, oacc[ot & 1][pg]);
           }
         }
@@ -915,21 +866,10 @@ __global__ __launch_bounds__(64 * (8 / PG_), 1) void mlp_gen_hp_kernel(MlpGParam
                 for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
                   for (int e8 = 0; e8 < 8; ++e8) m = fmaxf(m, fabsf(xval(pg, ks, e8)));
-                m = fmaxf(m, __shfl_xor(m, 16));
-                m = fmaxf(m, __shfl_xor(m, 32));
-                const float xi = pow2_below(m, 14, 120);
-                etap[pg] = pow2_below(m + 1.f, 14, 120);
-                ixi[pg] = 1.f / xi;
-                ietap[pg] = 1.f / etap[pg];
+                const float xi = set_range(pg, m);
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                  uint32_t t[2][4];
-#pragma unroll
-                  for (int e = 0; e < 4; ++e)
-                    split2h(xval(pg, ks, 2 * e) * xi, xval(pg, ks, 2 * e + 1) * xi, t[0][e], t[1][e]);
-#pragma unroll
-                  for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
-                }
+                for (int ks = 0; ks < KS; ++ks)
+                  x3h_split8([&](int e) { return xval(pg, ks, e) * xi; }, xf[pg][ks]);
               }
               prep(std::integral_constant<int, 0>{}, so_next);
             }
@@ -960,6 +900,19 @@ bool mg_shape(int Ct, int Cout, int* ks, int* ot) {
 }
 
 }  // namespace
+
+int launch_x3h_eta(const float* W1, const float* b1, int H, int Ct, float* eta, hipStream_t s) {
+  hipLaunchKernelGGL(x3h_eta_kernel, dim3(H), dim3(256), 0, s, W1, b1, Ct, eta);
+  return launch_check("x3h_eta");
+}
+
+int launch_x3h_row_scales(const float* W1, const float* W2, const float* eta, int H, int Ct,
+                          int Cout, int rows2, float* s1, float* s2, float* is1, float* is2,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(x3h_row_scale_kernel, dim3(H + rows2), dim3(256), 0, s, W1, W2, eta, H, Ct,
+                     Cout, s1, s2, is1, is2);
+  return launch_check("x3h_row_scale");
+}
 
 // MSFNO_MLP_GEN_H=0 keeps the two-GEMM x6 path for the standalone MLP
 static bool mlp_gen_h_env() {
@@ -1027,11 +980,8 @@ int launch_mlp_gen_h(const float* x, const float* xa, const float* xt, const flo
       set_error("mlp_gen_h: image clear failed");
       return MSFNO_EHIP;
     }
-    hipLaunchKernelGGL(mg_eta_kernel, dim3(H), dim3(256), 0, s, W1, b1, Ct, eta);
-    MSFNO_TRY(launch_check("mg_eta"));
-    hipLaunchKernelGGL(mg_scale_kernel, dim3(H + Cp), dim3(256), 0, s, W1, W2, eta, H, Ct, Cout,
-                       s1, s2, is1, is2);
-    MSFNO_TRY(launch_check("mg_scale"));
+    MSFNO_TRY(launch_x3h_eta(W1, b1, H, Ct, eta, s));
+    MSFNO_TRY(launch_x3h_row_scales(W1, W2, eta, H, Ct, Cout, Cp, s1, s2, is1, is2, s));
     hipLaunchKernelGGL(mg_image_kernel, dim3(256), dim3(256), 0, s, W1, W2, eta, s1, s2, H, Ct,
                        Cout, KS, OT, layout, img);
     MSFNO_TRY(launch_check("mg_image"));

@@ -2,7 +2,7 @@
 // convolution over pixels, on the block MLP's fc1 tiling (mlp_fused_h.hip: 16x16x32 fp16
 // MFMAs, 16 pixels per wave, fp32 as two fp16 terms and three MFMAs per product,
 // split_engine.h).  It shares that unit's 16-KB weight slice layout and ring depth
-// (MH_* in split_engine.h) and nothing else.
+// and the steps of the tile pipeline (x3h_tile.h) and nothing else.
 //   sk_prep_kernel          the per-batch weight image and its row scales
 //   skip_hp_kernel          the default: persistent, software-pipelined (P % 4 == 0)
 //   skip_h_kernel           one tile per workgroup (MSFNO_SKIP_P=0, any P)
@@ -11,9 +11,8 @@
 // NOPK_SRCS): without it skip_hp_kernel measured 1 % slower and took 20 bytes more
 // scratch (profiles/r11_mlp_io).  It has none of the op_sel form of DESIGN.md §5;
 // tests/test_mlp_packed_fp32.py and tests/test_isa_audit.py check the built library.
-#include "dma.h"
-#include "gemm_common.h"
 #include "kernels.h"
+#include "x3h_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -58,13 +57,7 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
   const int b = blockIdx.y, c = blockIdx.x, k = threadIdx.x;
   const float* row = W + (int64_t)c * MH_C;
   const float* xsb = xs ? xs + (int64_t)b * MH_C : nullptr;
-  float m = fabsf(xsb ? row[k] / xsb[k] : row[k]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((k & 63) == 0) wmax[k >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-  const float sc = row_scale(m, 15);
+  const float sc = row_scale(x3h_block_max(fabsf(xsb ? row[k] / xsb[k] : row[k]), wmax), 15);
   if (k == 0) {
     rs[(int64_t)b * MH_C + c] = sc;
     inv_rs[(int64_t)b * MH_C + c] = 1.f / sc;
@@ -72,15 +65,14 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
   if (k >= 128) return;
   const int k0 = 2 * k;  // the pair (k0, k0 + 1): one kh, ks, 8-channel group
   const int j = c >> 5, t = (c >> 4) & 1, r = c & 15;
-  const int kh = k0 >> 7, ks = (k0 >> 5) & 3, gq = (k0 >> 3) & 3;
-  const int kk = 8 * (gq ^ mlph_swz(r)) + (k0 & 7);  // its stored position in the 32-wide row
+  const int kh = k0 >> 7, ks = (k0 >> 5) & 3;
   uint32_t t0, t1;
   if (xsb)
     split2h(row[k0] / xsb[k0] * sc, row[k0 + 1] / xsb[k0 + 1] * sc, t0, t1);
   else
     split2h(row[k0] * sc, row[k0 + 1] * sc, t0, t1);
   unsigned short* ib = img + (int64_t)b * SK_NSLICE * MH_SLICE;
-  uint32_t* o = reinterpret_cast<uint32_t*>(ib + (int64_t)(j * 2 + kh) * MH_SLICE + ((ks * 2 + t) * 16 + r) * 32 + kk);
+  uint32_t* o = reinterpret_cast<uint32_t*>(ib + (int64_t)(j * 2 + kh) * MH_SLICE + x3h_w1_slice_pos(ks, t, r, k0 & 31));
   o[0] = t0;
   o[MH_PLANE / 2] = t1;
 }
@@ -104,17 +96,10 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
   const int64_t px = (int64_t)(lin - z * p.tiles_per_field) * 64 + 16 * wave + r16;
   const unsigned short* img = p.img + (int64_t)z * SK_NSLICE * MH_SLICE;
 
-  const uint32_t ring_lds = lds_addr(ring);
-  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  uint32_t piece_off[4];
+  const X3hRing<W, NS> wring(ring, wave, lane);
+  auto slice = [&](int q) { return img + (int64_t)q * MH_SLICE; };
 #pragma unroll
-  for (int i = 0; i < 4; ++i) piece_off[i] = (uint32_t)(i * W * 1024 + lane * 16);
-  auto issue = [&](int q) {
-    const uint64_t src = reinterpret_cast<uint64_t>(img + (int64_t)q * MH_SLICE) + (uint64_t)wave_u * 1024;
-    glds16x4<W * 1024>(src, piece_off, ring_lds + (uint32_t)((q % NS) * MH_SLICE * 2 + wave_u * 1024));
-  };
-#pragma unroll
-  for (int q = 0; q < NS; ++q) issue(q);
+  for (int q = 0; q < NS; ++q) wring.fill(q, slice(q));
 
   // x -> scaled fp16x2 B fragments (k-step ks: channels 32 ks + 8 g + 0..7)
   const float* xcol = p.x + (int64_t)z * MH_C * P + (px < P ? px : P - 1);
@@ -130,12 +115,7 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
       const float4 sa = *reinterpret_cast<const float4*>(xsb + c0);
       const float4 sb = *reinterpret_cast<const float4*>(xsb + c0 + 4);
       const float sv[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
-      uint32_t t[2][4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        split2h(sv[2 * e] * xv[2 * e], sv[2 * e + 1] * xv[2 * e + 1], t[0][e], t[1][e]);
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) xf[ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+      x3h_split8([&](int e) { return sv[e] * xv[e]; }, xf[ks]);
     }
   }
   for (int i = tid; i < MH_C; i += 256) {
@@ -148,21 +128,14 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
   floatx4 oacc[16];
 #pragma unroll
   for (int ot = 0; ot < 16; ++ot) oacc[ot] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
+  const int a_lane = x3h_a_lane(r16, g);
 
   // (the refill stays one burst: as four spread pieces the kernel alone measured 1.598
   // against 1.611 ms at config 2, 0.8 %, under twice the parent's own 0.44 % spread,
   // profiles/r09_refill/skip_h_alone.txt)
 #pragma unroll
   for (int q = 0; q < SK_NSLICE; ++q) {
-    // slice q landed (up to NS - 2 later slices may stay in flight); slot of q - 1 free
-    const int after = min(NS - 2, SK_NSLICE - 1 - q);
-    if (after >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (after == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const unsigned short* slot = ring + (q % NS) * MH_SLICE;
+    const unsigned short* slot = wring.landed(q, SK_NSLICE);
     const int j = q >> 1, kh = q & 1;
     auto aoff = [&](int u, int pl) { return ((pl * 4 + (u >> 1)) * 2 + (u & 1)) * 512 + a_lane; };
     half8 a[3][2];
@@ -178,7 +151,7 @@ __global__ __launch_bounds__(256, MINB) void skip_h_kernel(SkipHParams p) {
           a[(u + 2) % 3][pl] = *reinterpret_cast<const half8*>(slot + aoff(u + 2, pl));
       }
       SplitEng<2>::mma(a[u % 3], xf[kh * 4 + (u >> 1)], oacc[2 * j + (u & 1)]);
-      if (u == 0 && q >= 1 && q + NS - 1 < SK_NSLICE) issue(q + NS - 1);
+      if (u == 0) wring.refill(q, SK_NSLICE, slice);
     }
   }
 
@@ -369,19 +342,14 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
         const float4 sa = *reinterpret_cast<const float4*>(xsb + c0);
         const float4 sb = *reinterpret_cast<const float4*>(xsb + c0 + 4);
         const float sv[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
-        uint32_t t[2][4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          split2h(sv[2 * e] * xv[2 * e], sv[2 * e + 1] * xv[2 * e + 1], t[0][e], t[1][e]);
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl) xf[pg][ks][pl] = frag_cast<half8>(t[pl][0], t[pl][1], t[pl][2], t[pl][3]);
+        x3h_split8([&](int e) { return sv[e] * xv[e]; }, xf[pg][ks]);
       }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  const int a_lane = r16 * 32 + 8 * (g ^ mlph_swz(r16));
+  const int a_lane = x3h_a_lane(r16, g);
   float* const ep = epi_all + wave * 32 * SP_ERS;
   uint32_t xn[2][8][2][4];
 
@@ -481,9 +449,7 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
             e0[3 * SP_ERS] = fmaf(acc[3], is.w, bb.w);
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        x3h_wave_handover();
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int row = 8 * k + (lane >> 3), col = 4 * (lane & 7);
@@ -492,18 +458,14 @@ __global__ __launch_bounds__(64 * SP_W, 1) void skip_hp_kernel(SkipHPParams p) {
             __builtin_nontemporal_store(
                 v, reinterpret_cast<floatx4*>(ob + (int64_t)(32 * c + 8 * k) * P + so));
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        x3h_wave_handover();
       }
     }
 #pragma unroll
     for (int pg = 0; pg < 2; ++pg)
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-        for (int pl = 0; pl < 2; ++pl)
-          xf[pg][ks][pl] = frag_cast<half8>(xn[pg][ks][pl][0], xn[pg][ks][pl][1], xn[pg][ks][pl][2], xn[pg][ks][pl][3]);
+        x3h_frags(xn[pg][ks], xf[pg][ks]);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's dummy DMAs land before exit
 }
@@ -517,12 +479,8 @@ __global__ __launch_bounds__(256) void chan_pow2_scale_kernel(const float* __res
   const float* row = x + (int64_t)blockIdx.x * P;
   float m = 0.f;
   for (int64_t p = threadIdx.x; p < P; p += 256) m = fmaxf(m, fabsf(row[p]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    xs[blockIdx.x] = pow2_below(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])), 14, 120);
+  m = x3h_block_max(m, wmax);
+  if (threadIdx.x == 0) xs[blockIdx.x] = pow2_below(m, 14, 120);
 }
 
 }  // namespace

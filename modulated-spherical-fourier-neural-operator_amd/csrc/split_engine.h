@@ -114,20 +114,4 @@ __device__ __forceinline__ float pow2_below(float v, int t, int clamp) {
   return ldexpf(1.f, min(max(t - e, -clamp), clamp));
 }
 
-// The x3h MLP weight tile (mlp_fused_h.hip, skip_h.hip, mlp_gen_h.hip): 16 rows x 32 k fp16,
-// the four 16-B k-groups of row r XORed with mlph_swz(r) (conflict-free ds_read_b128
-// fragments); mlph_perm: the hidden row within a block of 32 that fc2's k position kappa
-// reads (the C layout of the fc1 accumulators is fc2's B fragment in place)
-__host__ __device__ __forceinline__ int mlph_swz(int r) { return ((r >> 2) & 1) << 1; }
-__host__ __device__ __forceinline__ int mlph_perm(int kappa) {
-  const int g = kappa >> 3, e = kappa & 7;
-  return e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4);
-}
-// The 16-KB fp16 weight slice built from those tiles and the depth of the LDS ring it streams
-// through, at C = 256: shared by the block MLP (mlp_fused_h.hip) and the inner skip (skip_h.hip)
-constexpr int MH_C = 256;
-constexpr int MH_PLANE = 4096;          // fp16 per plane within a slice
-constexpr int MH_SLICE = 2 * MH_PLANE;  // fp16 per 16-KB slice
-constexpr int MH_NS = 4;                // ring slots
-
 }  // namespace msfno

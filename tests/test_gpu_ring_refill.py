@@ -1,6 +1,7 @@
 """The MFMA kernels that refill an LDS ring by LDS-DMA while they compute
 (csrc/gemm_x6c.hip: the spectral-MLP layers; csrc/mlp_fused_h.hip: the fused block
-MLP; csrc/skip_h.hip: the two inner-skip kernels).  The spectral layers and the persistent skip issue
+MLP; csrc/skip_h.hip: the two inner-skip kernels; csrc/x3h_tile.h: X3hRing, the ring and its
+counted wait for the block MLP and the one-tile skip).  The spectral layers and the persistent skip issue
 a refill piece by piece between the MFMA groups of a step, the block MLP and the
 one-tile skip as one burst behind the step's first MFMAs; either way what orders a piece
 against the reads of its ring slot is a counted s_waitcnt and a barrier, so a miscount
@@ -29,7 +30,12 @@ Sizes: the smallest at which the loops take each of their paths.
                   of mlp_gen_h.hip and answers MSFNO_EUNSUPPORTED at 256 -> 512 -> 256), so
                   these cases run a whole C = 256 block on a grid of P points.
   inner skip      msfno_conv1x1, C = 256: P = 212 (the persistent kernel, P % 4 == 0)
-                  and P = 210 (one tile per workgroup).
+                  and P = 210 (one tile per workgroup), B = 2: four 128-pixel tiles on at
+                  least four workgroups, one tile each.  The persistent kernel's loop over
+                  tiles runs with B = 3, P = 260 on ONE workgroup (MSFNO_SKIP_GRID=0): nine
+                  tiles, the next tile's x through the ring, the scale tables reloaded at
+                  two field boundaries, each field ending on a 4-pixel tile, the tail's
+                  dummy groups.
 References: oracle/sfno_ref.py (layers.py:536-639 SpectralAttentionS2, :145-178 MLP,
 sfnonet.py:359-393 the block).
 """
@@ -201,10 +207,10 @@ def test_block_mlp(P, B, resid):
 
 # ---- inner skip ----------------------------------------------------------------------
 
-@pytest.mark.parametrize("P", [212, 210], ids=["skip_hp_P212", "skip_h_P210"])
-def test_inner_skip(P):
+def _inner_skip(B, P):
+    """msfno_conv1x1 at C = 256 three times: (inputs x, w, b on the CPU, output, repeatable)"""
     from msfno_amd import _native as N
-    B, C = 2, MLP_C
+    C = MLP_C
     g = torch.Generator().manual_seed(P)
     x = torch.randn(B, C, P, generator=g)
     w = torch.randn(C, C, generator=g) / C ** 0.5
@@ -220,10 +226,38 @@ def test_inner_skip(P):
         return out.cpu()
 
     got, same = _thrice(run)
-    assert same, "three runs on the same input differ"
+    return x, w, b, got, same
+
+
+def _inner_skip_bar(x, w, b, got, what):
     want64 = torch.einsum("oi,bip->bop", w.double(), x.double()) + b.double()[None, :, None]
     want32 = torch.einsum("oi,bip->bop", w, x) + b[None, :, None]
-    _bar(got, want64, want32, f"conv1x1 P={P}")
+    _bar(got, want64, want32, what)
+
+
+@pytest.mark.parametrize("P", [212, 210], ids=["skip_hp_P212", "skip_h_P210"])
+def test_inner_skip(P):
+    x, w, b, got, same = _inner_skip(2, P)
+    assert same, "three runs on the same input differ"
+    _inner_skip_bar(x, w, b, got, f"conv1x1 P={P}")
+
+
+def test_inner_skip_one_workgroup_many_tiles(monkeypatch):
+    """skip_hp_kernel's loop over tiles: B = 3, P = 260 is nine 128-pixel tiles (128, 128, 4
+    per field), and MSFNO_SKIP_GRID=0 (read on every call) makes launch_skip_h ask for
+    max(1, 0) = 1 workgroup, which walks all nine: x of tiles 1..8 arrives through the ring,
+    the scale tables are reloaded at two field boundaries, the last tile issues dummy groups.
+    The one-tile kernel (MSFNO_SKIP_P=0, also read on every call) forms every output from the
+    same products in the same order, and the two kernels agreed bit for bit on this input
+    before they shared csrc/x3h_tile.h, so that is asserted too."""
+    monkeypatch.setenv("MSFNO_SKIP_GRID", "0")
+    x, w, b, got, same = _inner_skip(3, 260)
+    assert same, "three runs on the same input differ"
+    _inner_skip_bar(x, w, b, got, "conv1x1 B=3 P=260, one workgroup")
+    monkeypatch.setenv("MSFNO_SKIP_P", "0")
+    _, _, _, one_tile, same = _inner_skip(3, 260)
+    assert same, "skip_h_kernel: three runs on the same input differ"
+    assert torch.equal(got, one_tile), "skip_hp_kernel and skip_h_kernel differ"
 
 
 if __name__ == "__main__":
