@@ -14,11 +14,16 @@
 // is applied to Re in the epilogue, before Ys = Re + Im is formed.
 //
 // Activations ("3M planes"): matrices 0 = real, 1 = imaginary, 2 = real + imaginary, three
-// bf16 planes each, stored in the tiled layout described at X6CParams below.
+// bf16 planes each (x3h: two fp16 planes), stored between the layers in MFMA fragment
+// order (described below X6CParams): a hidden layer's epilogue stores its accumulator
+// registers as they stand, and the next layer reads them back as B fragments with no
+// transpose; the permutation of the contraction index that this implies is carried
+// by the next layer's weight image.
 // Tile 128 complex rows x 128 columns x 16 (k), 8 waves as 4 (M) x 2 (N), each
 // wave 32 x 64 with three accumulator sets (P1, P2, P3).  Stage (72 KB) = A: 3
-// matrices x 3 planes x [128][16] + B: 3 x 3 x [16][128]; two stages, one k-tile
-// in flight (LDS-DMA, dma.h).  LDS swizzles as in gemm_x6p_kernel.
+// matrices x 3 planes x [128][16] + B: 3 x 3 x 16 x 128 (DMA-fed layers: four
+// 32-column blocks of 64 lanes x 8 k; layer 0: [16][128] rows, swizzled as in
+// gemm_x6p_kernel); two stages, one k-tile in flight (LDS-DMA, dma.h).
 
 #include "dma.h"
 #include "gemm_common.h"
@@ -65,12 +70,24 @@ struct X6CParams {
   int64_t cs_b;
 };
 
-// Tiled 3M activations (LAY): the planes of a layer's activation
-// stored as the LDS image of the next layer's B stages, [b][tn][kt][mat*3+plane][16
-// rows][128 columns, 8-column chunks XOR-swizzled by 4 (row & 3)]: one k-tile stage of
-// one column tile is a contiguous 36 KB, so the B DMA reads whole 1-KB pieces and the
-// epilogue writes whole rows of 256 B (the row layout reads 4 rows of 256 B at a
-// 130-KB stride per piece).  Pad rows (>= co) and columns (>= N) hold 0.
+// Tiled 3M activations (LAY): the planes of a layer's activation stored as the MFMA
+// B fragments of the next layer, [b][tn][kt][mat*NP+plane][cb = 0..3][lane 0..63][8]:
+// the 16 bytes of (cb, lane) are what lane (n = lane & 31, h = lane >> 5) feeds a
+// 32x32x16 MFMA as the B operand of column 32 cb + n of the tile, k positions
+// 8 h .. 8 h + 7 of k-tile kt.  That is also where the producing layer's accumulators
+// sit: of a 32-row output block, registers 8 t .. 8 t + 7 (t = 0, 1) of lane (n, h) are
+// rows 16 t + 8 (e >> 2) + 4 h + (e & 3), e = 0..7, of column n, so they are stored as
+// they stand as k-tile (row0 >> 4) + t, and k position kp = 8 h + e of a k-tile holds
+// channel 16 kt + x6c_kperm(kp).  The consuming layer's weight image carries the same
+// permutation of k (spec_weights_3m_kernel), and a sum over k does not see it.
+// One (matrix-plane, cb) is a contiguous 1 KB: one DMA piece, one wave store, and a
+// linear (conflict-free) ds_read_b128 per fragment.  Pad rows (>= co) and columns
+// (>= N) hold 0.
+__device__ __forceinline__ int x6c_kperm(int kp) {  // swaps the middle quads; an involution
+  return (kp & 3) | ((kp & 4) << 1) | ((kp & 8) >> 1);
+}
+// Layer 0 (BF32) stages its fp32 input itself, as a row-major [16 rows][128 columns]
+// LDS image with 8-column chunks XOR-swizzled by 4 (row & 3), read with transposing loads
 __device__ __forceinline__ int x6c_tile_swz(int r, int c) {
   return ((((c >> 3) ^ (4 * (r & 3)))) << 3) + (c & 7);
 }
@@ -132,7 +149,9 @@ __global__ void spec_scales_x3h_kernel(SpecWeightsX6p a) {
 
 // A image of one layer: Wr, Wi, Ws = Wr + Wi (co x ci each) from the reference
 // weight w (ci, co, 2), each split into [plane][kt][Mp][16]; NP = 2: scaled by
-// tau_l (a.scl) and split into two fp16 terms
+// tau_l (a.scl) and split into two fp16 terms.  Layer 0 reads fp32 rows and has its
+// channels in order along k; every later layer reads fragment-order planes and has
+// them in the planes' order within each k-tile (x6c_kperm; channels >= ci stay 0)
 template <int NP = 3>
 __global__ void spec_weights_3m_kernel(SpecWeightsX6p a) {
   const int64_t total = a.start[a.nlayers];
@@ -149,7 +168,10 @@ __global__ void spec_weights_3m_kernel(SpecWeightsX6p a) {
     const int64_t idx = 2 * f;
     const int kt = (int)(idx / ((int64_t)Mp * 16));
     const int rem = (int)(idx - (int64_t)kt * Mp * 16);
-    const int o = rem >> 4, k0 = kt * 16 + (rem & 15);
+    // l >= 1: the B operand arrives as fragment-order planes, whose k position kp of
+    // k-tile kt holds channel 16 kt + x6c_kperm(kp) (kp even: the pair stays a pair)
+    const int kp = rem & 15;
+    const int o = rem >> 4, k0 = kt * 16 + (l > 0 ? x6c_kperm(kp) : kp);
     const float tau = NP == 2 ? a.scl[2 * l] : 1.f;
     float v[2];
 #pragma unroll
@@ -224,7 +246,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   const unsigned short* X = p.X + z * p.x_b;
 
   // LDS-DMA pieces c = wave + NW q (q < NPC): c < APC -> A (matrix-plane c / 4, rows
-  // 32 (c % 4) ..), else B (matrix-plane (c - APC) / 4, k rows 4 ((c - APC) % 4) ..)
+  // 32 (c % 4) ..), else B (matrix-plane (c - APC) / 4, 32-column block (c - APC) % 4)
   // Each piece is addressed as a wave-uniform base that advances with the k-tile (A: the
   // weight image; B: this column tile's planes, tiled layout) plus the lane's 32-bit byte
   // offset voff, computed once (the hosts check that the weight image stays below 4 GB).
@@ -249,10 +271,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
       dst[q] = mp * A_PLANE + mb * 32 * BK;
       kind[q] = 0;
     } else {
-      const int cb = c - APC;
-      const int mp = cb >> 2, rq = cb & 3;
-      voff[q] = (uint32_t)((mp * B_PLANE + rq * 4 * BN + 8 * (lane & 15) + BN * (lane >> 4)) * 2);
-      dst[q] = A_ALL + mp * B_PLANE + rq * 4 * BN;
+      const int bp = c - APC;
+      const int mp = bp >> 2, cb = bp & 3;
+      voff[q] = (uint32_t)((mp * B_PLANE + cb * 512 + lane * 8) * 2);
+      dst[q] = A_ALL + mp * B_PLANE + cb * 512;
       kind[q] = 1;
     }
   }
@@ -348,8 +370,12 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
   int b_off[NT];
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
-    const int c = wn * WN + j * 32 + 16 * g16 + 4 * (li & 3);
-    b_off[j] = A_ALL + br * BN + (((c >> 3) ^ (4 * (br & 3))) << 3) + (c & 7);
+    if constexpr (BF32) {
+      const int c = wn * WN + j * 32 + 16 * g16 + 4 * (li & 3);
+      b_off[j] = A_ALL + br * BN + x6c_tile_swz(br, c);
+    } else {  // fragment-order planes: the lane's 16 bytes of 32-column block cb
+      b_off[j] = A_ALL + (wn * WN / 32 + j) * 512 + lane * 8;
+    }
   }
   // The MFMAs of one k-tile as NG groups (matrix mat, column tile j: MT x NP-engine
   // products), each accumulator seeing its products k-tile by k-tile in engine order.  The
@@ -375,12 +401,16 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl) {
         const unsigned short* q = base + (mat * NP + pl) * B_PLANE + b_off[j];
-        const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)q));
-        const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(q + 4 * BN)));
-        const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-        b[g & 1][pl] = __builtin_bit_cast(Frag, v);
+        if constexpr (!BF32) {  // the fragment as stored: one ds_read_b128
+          b[g & 1][pl] = *reinterpret_cast<const Frag*>(q);
+        } else {
+          const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)q));
+          const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_s16x4*)((__attribute__((address_space(3))) unsigned short*)(q + 4 * BN)));
+          const s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+          b[g & 1][pl] = __builtin_bit_cast(Frag, v);
+        }
       }
     };
     read_frags(0);
@@ -470,7 +500,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
     if (nk > 0) step(nk - 1, std::false_type{});
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  // the fp32 row epilogue goes through LDS: every wave is done with the ring first.
+  // (The plane epilogue stores from registers and touches no LDS.)
+  if constexpr (!PLANES_OUT) __syncthreads();
 
   // x3h: the layer multiplier (weight scale undone, output range) and, for the fp32
   // output rows of the last layer, the per-column factor (layer 0's input scale undone)
@@ -503,42 +535,37 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x6c_kernel(X6CParams p) {
         acc[1][i][j][r] = im;
         acc[2][i][j][r] = re + im;
       }
-  float* lds = reinterpret_cast<float*>(lds_raw);
-  GemmParams q{};
-  q.vecC = 1;
   if constexpr (PLANES_OUT) {
-    // tiled planes: every row and column of the tile (pad rows / columns are 0)
-    constexpr int CS_LD = BN + 8;
+    // fragment-order planes, every row and column of the tile (pad rows / columns are
+    // 0: zero weight rows, zero B columns).  Accumulator register r of lane (l32, half)
+    // is row 8 (r >> 2) + 4 half + (r & 3) of column l32 of its 32 x 32 block, so
+    // registers 8 t .. 8 t + 7 are, as they stand, the lane's B fragment of k-tile
+    // (block row >> 4) + t of the next layer (x6c_kperm): split in pairs and stored as
+    // 16 bytes per plane, 1 KB contiguous per wave.  No LDS, no barrier.
     unsigned short* Yt = p.Y + z * p.y_b + (int64_t)tn * p.kt_out * NMP * B_PLANE;
 #pragma unroll
-    for (int mat = 0; mat < 3; ++mat) {
+    for (int mat = 0; mat < 3; ++mat)
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            lds[(wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * CS_LD + wn * WN + j * 32 +
-                l32] = acc[mat][i][j][r];
-      __syncthreads();
-      constexpr int NQ = BM * BN / 4 / (64 * NW);
+          for (int t = 0; t < 2; ++t) {
+            const int kt = (m0 + wm * WM + 32 * i) / 16 + t, cb = wn * WN / 32 + j;
+            uint32_t w[4][NP];
 #pragma unroll
-      for (int qq = 0; qq < NQ; ++qq) {
-        const int idx = tid + 64 * NW * qq;
-        const int lr = idx / (BN / 4), c = 4 * (idx % (BN / 4));
-        const float4 v = *reinterpret_cast<const float4*>(lds + lr * CS_LD + c);
-        uint32_t ta[NP], tb[NP];
-        SplitEng<NP>::split(v.x, v.y, ta);
-        SplitEng<NP>::split(v.z, v.w, tb);
-        const int m = m0 + lr, r = m & 15;
-        unsigned short* d = Yt + ((int64_t)(m >> 4) * NMP + mat * NP) * B_PLANE + r * BN + x6c_tile_swz(r, c);
+            for (int e = 0; e < 4; ++e)
+              SplitEng<NP>::split(acc[mat][i][j][8 * t + 2 * e], acc[mat][i][j][8 * t + 2 * e + 1], w[e]);
+            unsigned short* d = Yt + (kt * NMP + mat * NP) * B_PLANE + cb * 512 + lane * 8;
 #pragma unroll
-        for (int pl = 0; pl < NP; ++pl)
-          *reinterpret_cast<uint2*>(d + pl * B_PLANE) = make_uint2(ta[pl], tb[pl]);
-      }
-      __syncthreads();
-    }
+            for (int pl = 0; pl < NP; ++pl)
+              *reinterpret_cast<uint4*>(d + pl * B_PLANE) =
+                  make_uint4(w[0][pl], w[1][pl], w[2][pl], w[3][pl]);
+          }
   } else {
+    float* lds = reinterpret_cast<float*>(lds_raw);
+    GemmParams q{};
+    q.vecC = 1;
 #pragma unroll
     for (int mat = 0; mat < 2; ++mat) {
       float* C = p.S + z * p.s_b + (mat ? p.s_im : 0);
