@@ -544,6 +544,33 @@ int msfno_spectrum_power_backward(const float* coeffs, const float* gpower, floa
                                   long long N, int lmax, int mmax, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Spherical Gaussian random fields: spectral coefficients of white or red-in-time (AR(1))
+ * noise in the layout msfno_sht_inverse reads (the Python side is
+ * msfno_amd/harmonics/random_fields.py).  The stream is a pure function of (seed, draw,
+ * global field index, l, m) ("Spherical Gaussian random fields"): Philox4x32-10
+ * with key (seed lo, seed hi) and counter (l * ceil(mmax / 2) + m / 2, field, draw lo,
+ * draw hi), Box-Muller on u = ((w >> 9) + 0.5) * 2^-23; xi = (z0, 0) for m = 0,
+ * (z0, z1) / sqrt(2) for 1 <= m <= l and exactly (0, 0) for m > l, where the output is
+ * zero whatever prev holds.  Independent of the launch geometry and of how fields are
+ * split over calls.  Neither call allocates or synchronises: both record into a graph.
+ * MSFNO_EINVAL for null coeffs or sqrt_eig, coefficient pointers off the 8-byte grid,
+ * an extent below 1, K < 1, lmax * ceil(mmax / 2) >= 2^32 or field0 + n > 2^32.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+/* coeffs (n, lmax, mmax) complex64 interleaved: the layout msfno_sht_inverse reads.
+ * sqrt_eig (K, lmax) fp32; local field i uses row (field0 + i) % K.
+ * out = a * prev + b * sqrt_eig[l] * xi(seed, draw, field0 + i, l, m)
+ * prev: NULL (then a is ignored) or (n, lmax, mmax) complex64; prev == coeffs is allowed
+ * (in place).  draw: the host value when draw_dev == NULL; otherwise the kernel reads
+ * *draw_dev (device uint64). */
+int msfno_noise_spectral(float* coeffs, const float* prev, const float* sqrt_eig, int K,
+                         long long n, long long field0, int lmax, int mmax, float a, float b,
+                         unsigned long long seed, unsigned long long draw,
+                         const unsigned long long* draw_dev, void* stream);
+/* *draw_dev += by, by one lane of one workgroup */
+int msfno_noise_advance(unsigned long long* draw_dev, unsigned long long by, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Latitude-band sharded SFNO-Block (multi-GPU form of
  * msfno_block_forward).  The reference runs one block per process on the whole
  * field (DDP = replicas, MSFNO/main.py:1153); this splits ONE field batch over

@@ -169,4 +169,30 @@ int msfno_spectrum_power_backward(const float* coeffs, const float* gpower, floa
                                         (hipStream_t)stream);
 }
 
+int msfno_noise_spectral(float* coeffs, const float* prev, const float* sqrt_eig, int K,
+                         long long n, long long field0, int lmax, int mmax, float a, float b,
+                         unsigned long long seed, unsigned long long draw,
+                         const unsigned long long* draw_dev, void* stream) {
+  MSFNO_REQUIRE(sqrt_eig && K >= 1 && field0 >= 0 &&
+                    spectrum_args_ok(coeffs, prev ? (const void*)prev : (const void*)coeffs, n,
+                                     lmax, mmax),
+                MSFNO_EINVAL, "bad noise_spectral arguments");
+  // the Philox counter holds l * ceil(mmax / 2) + m / 2 and the field index in 32 bits each
+  MSFNO_REQUIRE((int64_t)lmax * (((int64_t)mmax + 1) / 2) < (1LL << 32), MSFNO_EINVAL,
+                "noise_spectral: lmax * ceil(mmax / 2) must be below 2^32");
+  MSFNO_REQUIRE(field0 <= (1LL << 32) && n <= (1LL << 32) - field0, MSFNO_EINVAL,
+                "noise_spectral: field0 + n must not exceed 2^32");
+  return launch_noise_spectral(coeffs, prev, sqrt_eig, K, (int64_t)n, (int64_t)field0, lmax,
+                               mmax, a, b, (uint64_t)seed, (uint64_t)draw,
+                               reinterpret_cast<const uint64_t*>(draw_dev),
+                               (hipStream_t)stream);
+}
+
+int msfno_noise_advance(unsigned long long* draw_dev, unsigned long long by, void* stream) {
+  MSFNO_REQUIRE(draw_dev && (reinterpret_cast<uintptr_t>(draw_dev) & 7) == 0, MSFNO_EINVAL,
+                "bad noise_advance arguments");
+  return launch_noise_advance(reinterpret_cast<uint64_t*>(draw_dev), (uint64_t)by,
+                              (hipStream_t)stream);
+}
+
 }  // extern "C"

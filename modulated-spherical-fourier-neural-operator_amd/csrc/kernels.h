@@ -229,6 +229,16 @@ int launch_spectrum_power(const float* coeffs, float* power, int64_t rows, int m
 // dcoeffs[r][m] = (2 e_m gpower[r]) coeffs[r][m], e_0 = 1, e_m = 2 (m >= 1)
 int launch_spectrum_power_backward(const float* coeffs, const float* gpower, float* dcoeffs,
                                    int64_t rows, int mmax, hipStream_t s);
+// ---- noise.hip: spectral coefficients of a spherical Gaussian random field ----------------
+// coeffs (n, lmax, mmax) complex interleaved, 8-byte aligned:
+// coeffs = a prev + b sqrt_eig[(field0 + i) % K][l] xi(seed, draw, field0 + i, l, m); prev
+// null (a ignored) or as coeffs (may be coeffs itself); draw_dev (device) overrides draw
+int launch_noise_spectral(float* coeffs, const float* prev, const float* sqrt_eig, int K,
+                          int64_t n, int64_t field0, int lmax, int mmax, float a, float b,
+                          uint64_t seed, uint64_t draw, const uint64_t* draw_dev,
+                          hipStream_t s);
+// *draw_dev += by
+int launch_noise_advance(uint64_t* draw_dev, uint64_t by, hipStream_t s);
 // ---- vector.hip: the streams between the two scalar transforms of a vector transform ------
 // A (2bc, lmax + 1, mmax), B (2bc, lmax, mmax) complex -> st (bc, 2, lmax, mmax):
 // s = A_theta[l+1] - i B_phi[l], t = A_phi[l+1] + i B_theta[l]; zeros where l < m or l = 0

@@ -196,6 +196,9 @@ SIGNATURES = [
                                 ctypes.POINTER(GcnGrads), _vp, _i, _vp, _sz, _vp]),
     ("msfno_spectrum_power", _i, [_vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
     ("msfno_spectrum_power_backward", _i, [_vp, _vp, _vp, ctypes.c_longlong, _i, _i, _vp]),
+    ("msfno_noise_spectral", _i, [_vp, _vp, _vp, _i, ctypes.c_longlong, ctypes.c_longlong, _i, _i,
+                                  _f, _f, ctypes.c_ulonglong, ctypes.c_ulonglong, _vp, _vp]),
+    ("msfno_noise_advance", _i, [_vp, ctypes.c_ulonglong, _vp]),
     ("msfno_band_partition", _i, [_i, _i, _i, _i, _ip, _ip]),
     ("msfno_band_exchange_counts", _i, [_i, _i, _i, _i, _ip, _ip, _i, _i, _llp, _llp]),
     ("msfno_band_local_rows", _i, [_i, _i, _i, _ip, _ip, _ip]),

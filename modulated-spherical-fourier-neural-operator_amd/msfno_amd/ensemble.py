@@ -26,6 +26,9 @@ step into a slot, nothing synchronises); ``Rollout.verify_ensemble`` drives it.
 ``CRPSLoss`` is the training objective: the mean over (B, C) of
 ``(abs - kappa gini) / (nlon sum w)`` with ``kappa = 1 / (M (M - 1))`` (fair) or
 ``1 / M^2``, with the native gradient (``msfno_ens_crps_backward``) to the members only.
+
+``perturb`` makes the members of such a run from one state and a
+``harmonics.GaussianRandomFieldS2``.
 """
 from __future__ import annotations
 
@@ -74,6 +77,44 @@ def _check_members(ens, tar, w, grad_ok=False):
     _check_count(ens.shape[0])
     return F.check_fields(ens, tar, w, "ens", _members,
                           None if grad_ok else ("ensemble", "CRPSLoss"))
+
+
+@torch.no_grad()
+def perturb(x0, M, grf, amplitude=1.0, centred=True):
+    """(M, C, H, W) perturbed copies of the state ``x0`` (C, H, W) or (1, C, H, W): what
+    ``Rollout.verify_ensemble`` takes as its members.  ``grf`` is a
+    ``harmonics.GaussianRandomFieldS2`` on the (H, W) grid with one spectrum per channel
+    (K = C) or one for all; ``amplitude`` is a scalar or (C,) and scales the field, so with
+    ``harmonics.unit_variance`` spectra it is a standard deviation in the units of ``x0``.
+    ``centred``: members 2k and 2k + 1 are ``x0 + amplitude field_k`` and ``x0 - amplitude
+    field_k``, so the member mean is ``x0`` (M must be even); otherwise every member has a
+    field of its own.  Consumes one draw of ``grf``."""
+    _check_count(M)
+    if centred and M % 2:
+        raise ValueError(f"a centred ensemble has an even number of members, got {M}")
+    if x0.dim() == 4 and x0.shape[0] == 1:
+        x0 = x0[0]
+    if x0.dim() != 3:
+        raise ValueError(f"x0 must be (C, H, W) or (1, C, H, W), got {tuple(x0.shape)}")
+    C, H, W = x0.shape
+    if (H, W) != (grf.nlat, grf.nlon):
+        raise ValueError(f"x0 is on a {(H, W)} grid, the field on {(grf.nlat, grf.nlon)}")
+    if grf.nrows not in (1, C):
+        raise ValueError(f"the field has {grf.K} spectra, x0 has {C} channels")
+    x0 = N.require_device_f32(x0, "x0")
+    n = M // 2 if centred else M
+    # K = C: (n, C, H, W) as sampled; one spectrum: n * C independent fields of it
+    field = (grf(n) if grf.nrows == C and grf.K is not None else grf(n * C)).view(n, C, H, W)
+    amp = torch.as_tensor(amplitude, dtype=torch.float32, device=x0.device)
+    if amp.dim() > 1 or (amp.dim() == 1 and amp.shape[0] != C):
+        raise ValueError(f"amplitude must be a scalar or ({C},), got {tuple(amp.shape)}")
+    d = field * (amp.view(C, 1, 1) if amp.dim() else amp)
+    if not centred:
+        return x0 + d
+    out = torch.empty(M, C, H, W, dtype=torch.float32, device=x0.device)
+    out[0::2] = x0 + d
+    out[1::2] = x0 - d
+    return out
 
 
 def workspace(M: int, B: int, C: int, nlat: int, nlon: int, device) -> torch.Tensor:

@@ -146,9 +146,21 @@ class Rollout:
     backend: the collectives are recorded into the graph, model.py:327-331's
     per-step cost without the host launches); over gloo (host collectives) it steps
     eagerly, and a capture that fails on any rank makes every rank step eagerly
-    (``TorchComm.all_agree``)."""
+    (``TorchComm.all_agree``).
 
-    def __init__(self, model, means=None, stds=None, film=None, scale=1.0, graph=True):
+    ``noise`` is a ``harmonics.SphericalAR1`` whose ``lead`` is the state's (B, C): every
+    step is then ``x <- model(x) + noise.step()`` in normalised units, in the eager loop
+    and inside the captured graph alike (the process keeps its draw counter on the device,
+    so every replay draws anew).  ``run`` does not reset the process."""
+
+    def __init__(self, model, means=None, stds=None, film=None, scale=1.0, graph=True,
+                 noise=None):
+        if noise is not None and getattr(model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout with noise steps whole fields; band-sharded noise is not "
+                "implemented (the stream is defined per (field, l, m), so a band rank can "
+                "generate its share)")
+        self.noise = noise
         self.model = model
         self.means, self.stds = means, stds
         self.film, self.scale = film, scale
@@ -169,13 +181,18 @@ class Rollout:
         return (data - self.means) / self.stds
 
     def _step(self, x):
-        if self.film is None:
-            return self.model(x)
-        return self.model(x, self.film, self.scale)
+        y = self.model(x) if self.film is None else self.model(x, self.film, self.scale)
+        if self.noise is None:
+            return y
+        return y + self.noise.step()
 
     def _capture(self, x):
         self._state = x.clone()
+        # the warm-up must not advance the noise process
+        snap = None if self.noise is None else self.noise.snapshot()
         self._step(self._state)  # warm-up: plans, descriptors, allocator pools
+        if snap is not None:
+            self.noise.restore(snap)
         quiesce = getattr(getattr(self.model, "comm", None), "quiesce", None)
         if callable(quiesce):
             quiesce()  # no RCCL work of the warm-up left for the watchdog to poll
@@ -191,6 +208,9 @@ class Rollout:
         6 h steps starting from ``x0`` (raw fields unless ``normalised_input``)."""
         x = x0 if normalised_input else self.normalise(x0)
         x = x.contiguous()
+        if self.noise is not None and tuple(x.shape[:2]) != tuple(self.noise.lead):
+            raise ValueError(f"the noise process has lead {tuple(self.noise.lead)}, the state "
+                             f"is {tuple(x.shape)}")
         if self.use_graph and x.is_cuda and (self._graph is None or self._state.shape != x.shape):
             if getattr(self.model, "world", 1) == 1:
                 self._capture(x)
