@@ -460,6 +460,59 @@ int msfno_ens_crps_backward(const float* ens, long long member_stride, const flo
                             void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Ensemble products and the counts behind the threshold scores (the Python mirror is
+ * msfno_amd/ensemble.py: products, threshold_sums, finish_thresholds).  Members as
+ * msfno_ens_sums takes them: member i of slab s at ens + i * member_stride + s * nlat * nlon,
+ * 2 <= M <= 32, any member stride >= S * nlat * nlon, any 16-byte phase.  Inputs are finite:
+ * the caller's contract, it is not checked.
+ *   msfno_ens_products: per-pixel maps, one pass over the members, no workspace.  Every
+ *   output of *out is optional (NULL: not wanted, its work is not done; at least one is):
+ *     mean  (S, nlat, nlon)  x_0 + (1/M) sum_i d_i,  d_i = x_i - x_0
+ *     std   (S, nlat, nlon)  sqrt(sum_i (d_i - dm)^2 / (M - 1)),  dm = (1/M) sum_i d_i: the
+ *                            unbiased spread from differences, exactly 0 for equal members
+ *     min, max (S, nlat, nlon)  members, bit for bit
+ *     quant (nq, S, nlat, nlon)  level q_levels[l] of the sorted members x_(0) <= .. <=
+ *                            x_(M-1), linear interpolation: with pos = q (M - 1),
+ *                            lo = floor(pos), hi = min(lo + 1, M - 1), frac = pos - lo (formed
+ *                            on the host in fp64), x_(lo) + frac (x_(hi) - x_(lo)); where
+ *                            frac = 0 the member itself, bit for bit.  q_levels is a host
+ *                            array of nq <= 8 levels in [0, 1], read before the call returns.
+ *     prob  (nt, S, nlat, nlon)  #{i : x_i > thr[s][t]} (1/M), strict >; thr (S, nt) fp32 on
+ *                            the device, in field units per slab, nt <= 8
+ *   Every word of every wanted output is written.  A latitude band passes its own rows: the
+ *   maps are row-local.
+ *   msfno_ens_threshold_sums: per slab s and threshold t < nt <= 8, with
+ *   k = #{i : x_i > thr[s][t]} and o = [y > thr[s][t]] (strict > on both sides),
+ *     counts[s][t][0][k] = sum w_lat[h] [count == k],  k = 0..M
+ *     counts[s][t][1][k] = sum w_lat[h] [count == k] [o == 1]
+ *   counts (S, nt, 2, M + 1) fp32; tar (S, nlat, nlon), w_lat (nlat).  From them follow the
+ *   Brier score and its decomposition, the reliability diagram and the ROC curve.  A latitude
+ *   band passes its own rows and their weights; the counts of the bands add up.
+ *   Deterministic as msfno_ens_sums (integer counts per row and wave, one weighted add per row
+ *   and bin, waves in index order, chunks combined in fp64; no floating-point and no global
+ *   atomics); every word of counts is written by every call; the workspace may hold anything
+ *   on entry; nothing allocates, synchronises or memsets, so the calls record into a graph.
+ * MSFNO_EINVAL for null required pointers, *out with no output wanted, an extent below 1,
+ * M < 2, a member stride shorter than a member, a level outside [0, 1], quant wanted with
+ * nq < 1, prob wanted with nt < 1 or thr NULL, nq or nt below 0 (nt < 1 for the sums);
+ * MSFNO_EUNSUPPORTED for M > 32 or nq, nt > 8; MSFNO_EWORKSPACE for a short workspace; all
+ * before any launch.  The workspace size is 0 for arguments that the sums refuse.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+#define MSFNO_ENS_MAX_LEVELS 8
+typedef struct msfno_ens_products_out {
+  float *mean, *std, *min, *max, *quant, *prob;
+} msfno_ens_products_out;
+int msfno_ens_products(const float* ens, long long member_stride, const double* q_levels,
+                       int nq, const float* thr, int nt, const msfno_ens_products_out* out,
+                       int M, int S, int nlat, int nlon, void* stream);
+size_t msfno_ens_threshold_workspace_size(int S, int M, int nt, int nlat, int nlon);
+int msfno_ens_threshold_sums(const float* ens, long long member_stride, const float* tar,
+                             const float* w_lat, const float* thr, int nt,
+                             float* counts /* (S, nt, 2, M + 1) */, int M, int S, int nlat,
+                             int nlon, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Graph-convolution FiLM generator (MSFNO/Models/gcn/gcn.py:96-167 GCN_custom,
  * layers.py:8-43 GraphConvolution; the Python mirror is msfno_amd/filmgen.py): the network
  * that turns the ocean points of an SST field into the FiLM vector, and its backward.  Per

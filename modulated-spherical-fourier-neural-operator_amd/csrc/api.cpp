@@ -146,6 +146,64 @@ int msfno_ens_crps_backward(const float* ens, long long member_stride, const flo
                                   dens_member_stride, M, S, nlat, nlon, (hipStream_t)stream);
 }
 
+int msfno_ens_products(const float* ens, long long member_stride, const double* q_levels,
+                       int nq, const float* thr, int nt, const msfno_ens_products_out* out,
+                       int M, int S, int nlat, int nlon, void* stream) {
+  MSFNO_REQUIRE(ens && out && S > 0 && nlat > 0 && nlon > 0 && M >= 2 && nq >= 0 && nt >= 0,
+                MSFNO_EINVAL, "bad ens_products arguments");
+  MSFNO_REQUIRE(out->mean || out->std || out->min || out->max || out->quant || out->prob,
+                MSFNO_EINVAL, "ens_products: no output wanted");
+  MSFNO_REQUIRE(member_stride >= (long long)S * nlat * nlon, MSFNO_EINVAL,
+                "ens_products: member_stride is shorter than a member");
+  MSFNO_REQUIRE(!out->quant || (nq >= 1 && q_levels), MSFNO_EINVAL,
+                "ens_products: quant wanted without a level");
+  MSFNO_REQUIRE(!out->prob || (nt >= 1 && thr), MSFNO_EINVAL,
+                "ens_products: prob wanted without a threshold");
+  MSFNO_REQUIRE(M <= 32, MSFNO_EUNSUPPORTED, "ens_products: more than 32 members");
+  MSFNO_REQUIRE(nq <= MSFNO_ENS_MAX_LEVELS && nt <= MSFNO_ENS_MAX_LEVELS, MSFNO_EUNSUPPORTED,
+                "ens_products: more than 8 levels or thresholds");
+  // the position of level q among the sorted members, pos = q (M - 1), in fp64: the kernel
+  // never divides.  hi stays below M: the bucket's padding sorts behind the members.
+  EnsQuantiles eq = {};
+  for (int l = 0; out->quant && l < nq; ++l) {
+    const double q = q_levels[l];
+    MSFNO_REQUIRE(q >= 0.0 && q <= 1.0, MSFNO_EINVAL,
+                  "ens_products: a quantile level outside [0, 1]");
+    const double pos = q * (M - 1);
+    const int lo = std::min((int)std::floor(pos), M - 1);
+    eq.lo[l] = lo;
+    eq.hi[l] = std::min(lo + 1, M - 1);
+    eq.frac[l] = (float)(pos - lo);
+  }
+  const EnsProductsOut o = {out->mean, out->std, out->min, out->max, out->quant, out->prob};
+  return launch_ens_products(ens, member_stride, eq, nq, thr, nt, o, M, S, nlat, nlon,
+                             (hipStream_t)stream);
+}
+
+size_t msfno_ens_threshold_workspace_size(int S, int M, int nt, int nlat, int nlon) {
+  if (S <= 0 || M < 2 || M > 32 || nt < 1 || nt > MSFNO_ENS_MAX_LEVELS || nlat <= 0 || nlon <= 0)
+    return 0;
+  return ens_threshold_workspace_bytes(S, M, nt, nlat);
+}
+
+int msfno_ens_threshold_sums(const float* ens, long long member_stride, const float* tar,
+                             const float* w_lat, const float* thr, int nt, float* counts,
+                             int M, int S, int nlat, int nlon, void* ws, size_t ws_bytes,
+                             void* stream) {
+  MSFNO_REQUIRE(ens && tar && w_lat && thr && counts && ws && S > 0 && nlat > 0 && nlon > 0 &&
+                    M >= 2 && nt >= 1,
+                MSFNO_EINVAL, "bad ens_threshold_sums arguments");
+  MSFNO_REQUIRE(member_stride >= (long long)S * nlat * nlon, MSFNO_EINVAL,
+                "ens_threshold_sums: member_stride is shorter than a member");
+  MSFNO_REQUIRE(M <= 32, MSFNO_EUNSUPPORTED, "ens_threshold_sums: more than 32 members");
+  MSFNO_REQUIRE(nt <= MSFNO_ENS_MAX_LEVELS, MSFNO_EUNSUPPORTED,
+                "ens_threshold_sums: more than 8 thresholds");
+  MSFNO_REQUIRE(ws_bytes >= msfno_ens_threshold_workspace_size(S, M, nt, nlat, nlon),
+                MSFNO_EWORKSPACE, "ens_threshold_sums: workspace too small");
+  return launch_ens_threshold_sums(ens, member_stride, tar, w_lat, thr, nt, counts, M, S, nlat,
+                                   nlon, ws, (hipStream_t)stream);
+}
+
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on
 // the 8-byte grid
 static bool spectrum_args_ok(const void* a, const void* b, long long N, int lmax, int mmax) {

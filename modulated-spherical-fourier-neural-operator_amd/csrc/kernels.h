@@ -187,6 +187,27 @@ int launch_ens_sums(const float* ens, int64_t mstride, const float* tar, const f
 int launch_ens_crps_backward(const float* ens, int64_t mstride, const float* tar,
                              const float* w_lat, const float* g, float kappa, float* dens,
                              int64_t dstride, int M, int S, int nlat, int nlon, hipStream_t s);
+// ---- ens_products.hip: per-pixel ensemble products and the threshold counts -----------------
+constexpr int kEnsMaxLevels = 8;  // quantile levels, and thresholds, of one call
+// level l of the sorted members: x_(lo) + frac (x_(hi) - x_(lo)), hi = min(lo + 1, M - 1)
+struct EnsQuantiles {
+  int lo[kEnsMaxLevels], hi[kEnsMaxLevels];
+  float frac[kEnsMaxLevels];
+};
+// (S, nlat, nlon) each, quant (nq, S, nlat, nlon), prob (nt, S, nlat, nlon); null = not wanted
+struct EnsProductsOut {
+  float *mean, *std, *mn, *mx, *quant, *prob;
+};
+// members as launch_ens_sums takes them; thr (S, nt) on the device (read where prob is wanted)
+int launch_ens_products(const float* ens, int64_t mstride, const EnsQuantiles& q, int nq,
+                        const float* thr, int nt, const EnsProductsOut& out, int M, int S,
+                        int nlat, int nlon, hipStream_t s);
+// counts (S, nt, 2, M + 1): the weighted counts of k members above thr[s][t], and of those
+// where the truth is above it too; ws >= ens_threshold_workspace_bytes (may hold anything)
+size_t ens_threshold_workspace_bytes(int S, int M, int nt, int nlat);
+int launch_ens_threshold_sums(const float* ens, int64_t mstride, const float* tar,
+                              const float* w_lat, const float* thr, int nt, float* counts,
+                              int M, int S, int nlat, int nlon, void* ws, hipStream_t s);
 // ---- graph.hip: the graph-convolution FiLM generator (gcn.cpp) -----------------------------
 // node-major activations (nb N, hid), hid % 4 == 0, 16-byte aligned; CSR (rp N + 1, ci, av).
 // part (gcn_partial_bytes, may hold anything on entry) receives the fixed-order column

@@ -115,6 +115,17 @@ class GcnGrads(ctypes.Structure):
     ]
 
 
+ENS_MAX_LEVELS = 8
+
+
+class EnsProductsOut(ctypes.Structure):
+    """Mirror of ``msfno_ens_products_out`` (include/msfno.h): output pointers, NULL = not
+    wanted."""
+
+    _fields_ = [("mean", _vp), ("std", _vp), ("min", _vp), ("max", _vp), ("quant", _vp),
+                ("prob", _vp)]
+
+
 _ip = ctypes.POINTER(_i)
 _llp = ctypes.POINTER(ctypes.c_longlong)
 
@@ -189,6 +200,11 @@ SIGNATURES = [
                             _vp]),
     ("msfno_ens_crps_backward", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _f, _vp,
                                      ctypes.c_longlong, _i, _i, _i, _i, _vp]),
+    ("msfno_ens_products", _i, [_vp, ctypes.c_longlong, ctypes.POINTER(ctypes.c_double), _i, _vp,
+                                _i, ctypes.POINTER(EnsProductsOut), _i, _i, _i, _i, _vp]),
+    ("msfno_ens_threshold_workspace_size", _sz, [_i, _i, _i, _i, _i]),
+    ("msfno_ens_threshold_sums", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
+                                      _i, _vp, _sz, _vp]),
     ("msfno_gcn_workspace_size", _sz, [_i, _i, _i, _i, _i, _i, _i]),
     ("msfno_gcn_forward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp, _vp, _i,
                                _i, _vp, _sz, _vp]),

@@ -29,9 +29,22 @@ step into a slot, nothing synchronises); ``Rollout.verify_ensemble`` drives it.
 
 ``perturb`` makes the members of such a run from one state and a
 ``harmonics.GaussianRandomFieldS2``.
+
+``products`` turns the members into the maps a forecast is issued as (``msfno_ens_products``,
+csrc/ens_products.hip): the ensemble mean and spread (from differences ``x_i - x_0``), the
+extremes, quantiles of the sorted members (linear interpolation) and the probability of
+exceeding a threshold, in one pass, each output optional.  The maps are row-local: a
+latitude-band rank calls it on its own rows.  ``threshold_sums`` leaves, per (batch, channel)
+and threshold, the weighted counts of pixels with k members above the threshold and of those
+where the truth is above it too (``msfno_ens_threshold_sums``; additive over rows, so a band
+rank passes its rows and ``w[rows]`` and all-reduces); ``finish_thresholds`` turns them into
+the Brier score with its decomposition, the reliability diagram and the ROC curve.
+``EnsembleVerifier(..., thresholds=)`` keeps them per scored step.  Inputs are finite: that
+is the caller's contract and is not checked.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from collections import namedtuple
 
@@ -45,6 +58,14 @@ NSUMS = 5
 SE, ERR, ABS, GINI, SQ = range(NSUMS)
 MAX_MEMBERS = 32
 
+MAX_LEVELS = N.ENS_MAX_LEVELS
+
+EnsembleProducts = namedtuple("EnsembleProducts", ["mean", "std", "min", "max", "quantiles",
+                                                   "prob"])
+ThresholdScores = namedtuple("ThresholdScores", ["base_rate", "brier", "fair_brier",
+                                                 "reliability", "resolution", "uncertainty",
+                                                 "forecast_hist", "observed_freq", "hit_rate",
+                                                 "false_alarm_rate", "roc_area"])
 EnsembleScores = namedtuple("EnsembleScores", ["mse", "rmse", "bias", "mae", "crps", "fair_crps",
                                                "spread", "spread_skill", "rank_hist"])
 
@@ -177,14 +198,207 @@ def finish(sums, hist, w, nlon, M) -> EnsembleScores:
                           None if hist is None else hist.to(sums.dtype) / n)
 
 
+def quantile_position(q: float, M: int):
+    """(lo, hi, frac) of level ``q`` among M sorted members, as the C side forms it in fp64:
+    ``pos = q (M - 1)``, ``lo = floor(pos)``, ``hi = min(lo + 1, M - 1)``, ``frac = pos - lo``;
+    the value is ``x_(lo) + frac (x_(hi) - x_(lo))`` (torch's linear interpolation)."""
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"a quantile level must be in [0, 1], got {q}")
+    pos = float(q) * (M - 1)
+    lo = min(int(math.floor(pos)), M - 1)
+    return lo, min(lo + 1, M - 1), pos - lo
+
+
+def _thresholds(thr, B, C, device):
+    """``thr`` (C, nt) or (B, C, nt) as fp32 device (B, C, nt), contiguous."""
+    thr = N.require_device_f32(thr, "thresholds")
+    if thr.dim() == 2:
+        thr = thr.unsqueeze(0).expand(B, *thr.shape)
+    if thr.dim() != 3 or tuple(thr.shape[:2]) != (B, C) or thr.shape[2] < 1:
+        raise ValueError(f"thresholds must be ({C}, nt) or ({B}, {C}, nt) with nt >= 1, got "
+                         f"{tuple(thr.shape)}")
+    if thr.device != device:
+        raise ValueError("ens and thresholds must be on one device")
+    return thr.contiguous()
+
+
+@N.on_input_device
+def _products_launch(ens, levels, thr, out):
+    """One call of at most MAX_LEVELS levels and thresholds; ``out`` maps the names of
+    ``msfno_ens_products_out`` to tensors."""
+    M, B, C, H, W = ens.shape
+    q = (ctypes.c_double * max(1, len(levels)))(*levels)
+    o = N.EnsProductsOut(**{k: N.ptr(v) for k, v in out.items()})
+    nt = 0 if thr is None else thr.shape[-1]
+    N.check(N.lib().msfno_ens_products(ens.data_ptr(), ens.stride(0), q, len(levels),
+                                       N.ptr(thr), nt, ctypes.byref(o), M, B * C, H, W,
+                                       N.stream_of(ens.device)), "msfno_ens_products")
+
+
+@torch.no_grad()
+def products(ens, quantiles=(), thresholds=None, mean=True, std=True, minmax=False):
+    """``EnsembleProducts(mean, std, min, max, quantiles, prob)`` of the members ``ens``
+    (M, B, C, H, W), per pixel; fields not asked for are None.  ``mean`` and ``std`` (the
+    unbiased spread, exactly 0 for equal members) are formed from the differences
+    ``x_i - x_0``; ``min`` and ``max`` (``minmax``) are members bit for bit; ``quantiles``
+    (nq, B, C, H, W) are the levels ``quantiles`` in [0, 1] of the sorted members with linear
+    interpolation (torch's default), a member bit for bit where the level falls on one;
+    ``prob`` (nt, B, C, H, W) is the fraction of members strictly above ``thresholds``
+    ((C, nt) or (B, C, nt), in field units).  One native pass; more than 8 levels or
+    thresholds take one more pass per 8.  The members may be views into a larger buffer (any
+    member stride) and must be finite (not checked).  2 <= M <= 32.  No gradient.  The maps
+    are row-local: a latitude-band rank passes its own rows."""
+    if ens.dim() != 5:
+        raise ValueError(f"ens must be (M, B, C, H, W), got {tuple(ens.shape)}")
+    _check_count(ens.shape[0])
+    if ens.requires_grad:
+        raise ValueError("ens requires grad: the ensemble products have no gradient; pass "
+                         "ens.detach() (for training use CRPSLoss)")
+    ens = _members(ens)
+    if ens.numel() == 0:
+        raise ValueError("empty fields")
+    M, B, C, H, W = ens.shape
+    levels = [float(q) for q in quantiles]
+    for q in levels:
+        quantile_position(q, M)
+    thr = None if thresholds is None else _thresholds(torch.as_tensor(thresholds), B, C,
+                                                      ens.device)
+    if not (mean or std or minmax or levels or thr is not None):
+        raise ValueError("no product asked for")
+
+    def new(*lead):
+        return torch.empty(*lead, B, C, H, W, dtype=torch.float32, device=ens.device)
+
+    res = dict(mean=new() if mean else None, std=new() if std else None,
+               min=new() if minmax else None, max=new() if minmax else None,
+               quant=new(len(levels)) if levels else None,
+               prob=new(thr.shape[-1]) if thr is not None else None)
+    nt = 0 if thr is None else thr.shape[-1]
+    first = True
+    for a in range(0, max(len(levels), nt, 1), MAX_LEVELS):
+        lv = levels[a:a + MAX_LEVELS]
+        th = None if thr is None or a >= nt else thr[..., a:a + MAX_LEVELS].contiguous()
+        out = {k: res[k] if first else None for k in ("mean", "std", "min", "max")}
+        out["quant"] = res["quant"][a:a + MAX_LEVELS] if lv else None
+        out["prob"] = res["prob"][a:a + MAX_LEVELS] if th is not None else None
+        _products_launch(ens, lv, th, out)
+        first = False
+    return EnsembleProducts(res["mean"], res["std"], res["min"], res["max"], res["quant"],
+                            res["prob"])
+
+
+def threshold_workspace(M: int, B: int, C: int, nt: int, nlat: int, nlon: int,
+                        device) -> torch.Tensor:
+    """A workspace for ``msfno_ens_threshold_sums`` at this shape and up to MAX_LEVELS
+    thresholds a call (contents do not matter)."""
+    nbytes = N.lib().msfno_ens_threshold_workspace_size(B * C, M, min(nt, MAX_LEVELS), nlat,
+                                                        nlon)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+@N.on_input_device
+def _threshold_launch(ens, tar, w, thr, counts, ws):
+    """``counts`` (B, C, nt, 2, M + 1), written whole; more than MAX_LEVELS thresholds in
+    calls of MAX_LEVELS (through a contiguous block of counts each)."""
+    M, B, C, H, W = ens.shape
+    nt = thr.shape[-1]
+    for a in range(0, nt, MAX_LEVELS):
+        n = min(MAX_LEVELS, nt - a)
+        whole = a == 0 and n == nt
+        th = thr if whole else thr[..., a:a + n].contiguous()
+        c = counts if whole else torch.empty(B, C, n, 2, M + 1, dtype=torch.float32,
+                                             device=ens.device)
+        N.check(N.lib().msfno_ens_threshold_sums(
+            ens.data_ptr(), ens.stride(0), tar.data_ptr(), w.data_ptr(), th.data_ptr(), n,
+            c.data_ptr(), M, B * C, H, W, ws.data_ptr(), ws.numel(), N.stream_of(ens.device)),
+            "msfno_ens_threshold_sums")
+        if not whole:
+            counts[:, :, a:a + n] = c
+    return counts
+
+
+@torch.no_grad()
+def threshold_sums(ens, tar, w, thresholds):
+    """(B, C, nt, 2, M + 1) fp32 weighted counts of the members ``ens`` (M, B, C, H, W) and
+    the truth ``tar`` (B, C, H, W) against ``thresholds`` ((C, nt) or (B, C, nt), in field
+    units) under the latitude weights ``w``: with k the number of members strictly above the
+    threshold at a pixel, ``[..., 0, k]`` is the weight of the pixels with that k and
+    ``[..., 1, k]`` of those among them where the truth is strictly above it too.  Additive
+    over rows (a latitude-band rank passes its rows and ``w[rows]`` and all-reduces), exact
+    integer counts per row, no atomics on floats: two calls give the same bits.  No
+    gradient."""
+    for n, t in (("ens", ens), ("tar", tar), ("w", w)):
+        if t.requires_grad:
+            raise ValueError(f"{n} requires grad: the threshold sums have no gradient; pass "
+                             f"{n}.detach() (for training use CRPSLoss)")
+    ens, tar, w = _check_members(ens, tar, w, grad_ok=True)
+    M, B, C, H, W = ens.shape
+    thr = _thresholds(torch.as_tensor(thresholds), B, C, ens.device)
+    counts = torch.empty(B, C, thr.shape[-1], 2, M + 1, dtype=torch.float32, device=ens.device)
+    return _threshold_launch(ens, tar, w, thr, counts,
+                             threshold_workspace(M, B, C, thr.shape[-1], H, W, ens.device))
+
+
+def finish_thresholds(counts, w, nlon, M) -> ThresholdScores:
+    """Scores of the probability forecasts ``p_k = k / M`` of the event "above the
+    threshold" from (..., 2, M + 1) counts taken under the weights ``w`` of the whole grid,
+    in the dtype of ``counts``.  With n = nlon * sum(w), N_k = counts[..., 0, k],
+    O_k = counts[..., 1, k] and obar = sum_k O_k / n:
+
+        base_rate = obar
+        brier = sum_k [p_k^2 (N_k - O_k) + (1 - p_k)^2 O_k] / n
+        fair_brier = brier - sum_k N_k k (M - k) / (M^2 (M - 1)) / n   (unbiased in M)
+        reliability = sum_k N_k (p_k - O_k / N_k)^2 / n     (bins with N_k = 0 give 0)
+        resolution = sum_k N_k (O_k / N_k - obar)^2 / n
+        uncertainty = obar (1 - obar);  brier = reliability - resolution + uncertainty
+        forecast_hist = N_k / n, observed_freq = O_k / N_k  (the reliability diagram; NaN
+                                                            where N_k = 0)
+        hit_rate[j], false_alarm_rate[j], j = 0..M + 1: of "warn when k >= j", from (1, 1) to
+        (0, 0); roc_area their trapezoid
+
+    Where the base rate is 0 (1) the hit rate (false alarm rate) and the ROC area are NaN,
+    as the plain division gives; the Brier terms stay finite."""
+    if M < 2:
+        raise ValueError(f"an ensemble has at least 2 members, got {M}")
+    if counts.dim() < 2 or tuple(counts.shape[-2:]) != (2, M + 1):
+        raise ValueError(f"counts must be (..., 2, {M + 1}), got {tuple(counts.shape)}")
+    n = F.grid_weight(w, nlon, counts.device).to(counts.dtype)
+    Nk, Ok = counts[..., 0, :], counts[..., 1, :]
+    k = torch.arange(M + 1, dtype=counts.dtype, device=counts.device)
+    p = k / M
+    # sums over k >= j, j = 0..M + 1 (the last is 0): the events and the non-events warned of;
+    # their totals are the first entries, so the curves start at (1, 1) exactly
+    zero = torch.zeros_like(Ok[..., :1])
+    miss = Nk - Ok
+    hits = torch.cat([Ok.flip(-1).cumsum(dim=-1).flip(-1), zero], dim=-1)
+    fals = torch.cat([miss.flip(-1).cumsum(dim=-1).flip(-1), zero], dim=-1)
+    obar = hits[..., 0] / n
+    brier = (p * p * miss + (1 - p) ** 2 * Ok).sum(dim=-1) / n
+    fair = brier - (Nk * (k * (M - k))).sum(dim=-1) / (M * M * (M - 1)) / n
+    some = Nk > 0
+    freq = Ok / Nk
+    f0 = torch.where(some, freq, torch.zeros_like(freq))
+    rel = (Nk * (p - f0) ** 2).sum(dim=-1) / n
+    res = (Nk * torch.where(some, f0 - obar[..., None], torch.zeros_like(f0)) ** 2).sum(dim=-1) / n
+    hr = hits / hits[..., :1]
+    far = fals / fals[..., :1]
+    area = ((far[..., :-1] - far[..., 1:]) * (hr[..., :-1] + hr[..., 1:])).sum(dim=-1) / 2
+    return ThresholdScores(obar, brier, fair, rel, res, obar * (1 - obar), Nk / n, freq, hr, far,
+                           area)
+
+
 class EnsembleVerifier(F.SlotVerifier):
     """The sums and rank counts of ``n_scored`` scored steps of an M-member rollout of
     (B, C, nlat, nlon) fields, in preallocated (n_scored, B, C, 5) ``sums`` and
     (n_scored, B, C, M + 1) ``hist`` device tensors with one workspace.  ``weights`` as
     ``verification.Verifier`` takes them.  ``update`` launches into a slot and never
-    synchronises, so it records into a graph; a slot that was never updated holds NaN."""
+    synchronises, so it records into a graph; a slot that was never updated holds NaN.
 
-    def __init__(self, weights, nlat, nlon, n_scored, M, B, C, device="cuda"):
+    With ``thresholds`` ((C, nt) or (B, C, nt), in field units) it also keeps the threshold
+    counts of every scored step in a (n_scored, B, C, nt, 2, M + 1) ``tcounts`` (one more
+    launch pair per ``update``, a second workspace); ``threshold_scores`` finishes them."""
+
+    def __init__(self, weights, nlat, nlon, n_scored, M, B, C, device="cuda", thresholds=None):
         _check_count(M)
         super().__init__(weights, nlat, nlon, n_scored, B, C, device)
         self.M = M
@@ -192,6 +406,13 @@ class EnsembleVerifier(F.SlotVerifier):
         self.sums = self._alloc(NSUMS)
         self.hist = self._alloc(M + 1)
         self._ws = workspace(M, B, C, nlat, nlon, self.device)
+        if thresholds is not None:
+            thr = torch.as_tensor(thresholds).detach().to(self.device)
+            self.thresholds = _thresholds(thr, B, C, self.device)
+            nt = self.thresholds.shape[-1]
+            self.tcounts = torch.full((n_scored, B, C, nt, 2, M + 1), float("nan"),
+                                      dtype=torch.float32, device=self.device)
+            self._tws = threshold_workspace(M, B, C, nt, nlat, nlon, self.device)
 
     @torch.no_grad()
     def update(self, k, ens, tar):
@@ -200,11 +421,20 @@ class EnsembleVerifier(F.SlotVerifier):
         self._check_slot(k, ens, "members")
         ens, tar, w = _check_members(ens, self._on_device(tar), self.w)
         _launch(ens, tar, w, self.sums[k], self.hist[k], self._ws)
+        if getattr(self, "tcounts", None) is not None:
+            _threshold_launch(ens, tar, w, self.thresholds, self.tcounts[k], self._tws)
 
     def scores(self) -> EnsembleScores:
         """``finish`` of all slots: EnsembleScores of (n_scored, B, C) tensors and the
         (n_scored, B, C, M + 1) rank histograms."""
         return finish(self.sums, self.hist, self.w, self.shape[4], self.M)
+
+    def threshold_scores(self) -> ThresholdScores:
+        """``finish_thresholds`` of all slots: ThresholdScores of (n_scored, B, C, nt)
+        tensors (and their (…, M + 1) and (…, M + 2) curves)."""
+        if getattr(self, "tcounts", None) is None:
+            raise ValueError("this verifier was built without thresholds")
+        return finish_thresholds(self.tcounts, self.w, self.shape[4], self.M)
 
 
 @N.on_input_device

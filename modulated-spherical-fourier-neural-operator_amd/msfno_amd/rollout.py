@@ -325,3 +325,30 @@ class Rollout:
             verifier.update(i // every, y.contiguous().view(M, 1, C, H, W),
                             tar.reshape(1, C, H, W))
         return verifier.scores()
+
+    def ensemble_products(self, x0, steps, every=1, normalised_input=False, **products_kwargs):
+        """An iterator of ``(step, ensemble.EnsembleProducts)`` for every step ``i`` of an ensemble
+        rollout where ``i % every == 0``: the batch of ``x0`` (M, C, H, W) is the M members
+        of one case, stepped together by ``run(x0, steps)``, and the products are those of
+        the denormalised output, viewed as (M, 1, C, H, W) without a copy, so the maps are
+        (1, C, H, W) (quantiles and prob (n, 1, C, H, W)).  ``products_kwargs`` go to
+        ``ensemble.products`` (``quantiles``, ``thresholds``, ``mean``, ``std``,
+        ``minmax``)."""
+        from . import ensemble as E
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.ensemble_products maps whole fields; on a latitude-band rank call "
+                "ensemble.products on the rank's rows: the maps are row-local, nothing is "
+                "exchanged")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        if x0.dim() != 4:
+            raise ValueError(f"x0 must be (M, C, H, W), got {tuple(x0.shape)}")
+        M, C, H, W = x0.shape
+
+        def maps():
+            for i, y in self.run(x0, steps, normalised_input=normalised_input):
+                if i % every == 0:
+                    yield i, E.products(y.contiguous().view(M, 1, C, H, W), **products_kwargs)
+
+        return maps()  # the refusals above are raised by the call, not by the first next()
