@@ -513,6 +513,48 @@ int msfno_ens_threshold_sums(const float* ens, long long member_stride, const fl
                              int nlon, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Forecast export: 16-bit simple packing of selected fields on the device, and its decode
+ * (the Python mirror is msfno_amd/export.py: pack, unpack, ForecastWriter).  x is (S_in,
+ * nlat, nlon) fp32 at any 4-byte alignment.  Per output slab s, over the selected points
+ * only, in fp32:
+ *     lo = min x, hi = max x, d = hi - lo, ref[s] = lo
+ *     exp2[s] = E = 0 where d == 0, else the smallest integer with d <= 65535 * 2^E, at
+ *               least -126 (every 65535 * 2^E is exact in fp32: no logarithm is taken)
+ *     q = (uint16) rint((x - ref) * 2^-E)   round to nearest even, clamped to [0, 65535];
+ *                                           the product with a power of two is exact
+ *     decode: xhat = ref + (float)q * 2^E   so |xhat - x| <= 2^(E-1) + ulp(d)/2 + ulp(xhat)/2
+ *   The encoding is that of GRIB simple packing with a binary scale, and of a netCDF / zarr
+ *   scale_factor = 2^E, add_offset = ref.  A numpy fp32 restatement gives the same bits.
+ *   Inputs are finite and so is hi - lo: the caller's contract, it is not checked.
+ *   Selection: slab (S_out) int32 on the device gives the source slab of each output slab
+ *   (any order, repeats allowed; not range-checked on the device, as clim_slab is not;
+ *   NULL: output slab s is slab s, S_out <= S_in); *win picks the rows lat0 + i lat_step,
+ *   i < nlat_out, and the columns lon0 + j lon_step, j < nlon_out, of a slab (a host
+ *   struct read before the call returns; NULL: the whole slab).  The range is that of the
+ *   selected points: a subset gets the precision of its own range.
+ *   msfno_pack16 writes ref (S_out), exp2 (S_out) and q (S_out, nlat_out, nlon_out), dense.
+ *   msfno_unpack16 decodes S slabs of n_per_slab values into y at any 4-byte alignment.
+ *   Deterministic (min and max do not depend on an order; no atomics); every word of ref,
+ *   exp2, q and y is written by every call; the workspace may hold anything on entry;
+ *   nothing allocates, synchronises or memsets, so the calls record into a graph.
+ * MSFNO_EINVAL for null required pointers, an extent or a step below 1, S_out > S_in without
+ * a slab list, a window that leaves the slab (lat0 + (nlat_out - 1) lat_step >= nlat,
+ * likewise in longitude, or a negative origin); MSFNO_EWORKSPACE for a short workspace; all
+ * before any launch.  The workspace size is 0 for arguments that the call refuses.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+typedef struct msfno_window {
+  int lat0, lat_step, nlat_out, lon0, lon_step, nlon_out;
+} msfno_window;
+size_t msfno_pack16_workspace_size(int S_out, int nlat_out, int nlon_out);
+int msfno_pack16(const float* x, int S_in, int nlat, int nlon, const int* slab, int S_out,
+                 const msfno_window* win, float* ref /* (S_out) */, int* exp2 /* (S_out) */,
+                 unsigned short* q /* (S_out, nlat_out, nlon_out), dense */, void* ws,
+                 size_t ws_bytes, void* stream);
+int msfno_unpack16(const unsigned short* q, const float* ref, const int* exp2, float* y,
+                   long long n_per_slab, int S, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Graph-convolution FiLM generator (MSFNO/Models/gcn/gcn.py:96-167 GCN_custom,
  * layers.py:8-43 GraphConvolution; the Python mirror is msfno_amd/filmgen.py): the network
  * that turns the ocean points of an SST field into the FiLM vector, and its backward.  Per

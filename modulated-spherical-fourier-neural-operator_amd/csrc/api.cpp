@@ -204,6 +204,40 @@ int msfno_ens_threshold_sums(const float* ens, long long member_stride, const fl
                                    nlon, ws, (hipStream_t)stream);
 }
 
+size_t msfno_pack16_workspace_size(int S_out, int nlat_out, int nlon_out) {
+  if (S_out <= 0 || nlat_out <= 0 || nlon_out <= 0) return 0;
+  return pack16_workspace_bytes(S_out, nlat_out);
+}
+
+int msfno_pack16(const float* x, int S_in, int nlat, int nlon, const int* slab, int S_out,
+                 const msfno_window* win, float* ref, int* exp2, unsigned short* q, void* ws,
+                 size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(x && ref && exp2 && q && ws && S_in > 0 && nlat > 0 && nlon > 0 && S_out > 0,
+                MSFNO_EINVAL, "bad pack16 arguments");
+  MSFNO_REQUIRE(slab || S_out <= S_in, MSFNO_EINVAL,
+                "pack16: more output slabs than slabs without a slab list");
+  const msfno_window whole = {0, 1, nlat, 0, 1, nlon};
+  const msfno_window& v = win ? *win : whole;
+  MSFNO_REQUIRE(v.lat_step >= 1 && v.lon_step >= 1 && v.nlat_out >= 1 && v.nlon_out >= 1,
+                MSFNO_EINVAL, "pack16: a window extent or step below 1");
+  MSFNO_REQUIRE(v.lat0 >= 0 && v.lon0 >= 0 &&
+                    v.lat0 + (long long)(v.nlat_out - 1) * v.lat_step < nlat &&
+                    v.lon0 + (long long)(v.nlon_out - 1) * v.lon_step < nlon,
+                MSFNO_EINVAL, "pack16: the window leaves the slab");
+  MSFNO_REQUIRE(ws_bytes >= msfno_pack16_workspace_size(S_out, v.nlat_out, v.nlon_out),
+                MSFNO_EWORKSPACE, "pack16: workspace too small");
+  const PackWin w = {nlat, nlon, v.lat0, v.lat_step, v.lon0, v.lon_step};
+  return launch_pack16(x, slab, w, S_out, v.nlat_out, v.nlon_out, ref, exp2, q, ws,
+                       (hipStream_t)stream);
+}
+
+int msfno_unpack16(const unsigned short* q, const float* ref, const int* exp2, float* y,
+                   long long n_per_slab, int S, void* stream) {
+  MSFNO_REQUIRE(q && ref && exp2 && y && n_per_slab > 0 && S > 0, MSFNO_EINVAL,
+                "bad unpack16 arguments");
+  return launch_unpack16(q, ref, exp2, y, n_per_slab, S, (hipStream_t)stream);
+}
+
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on
 // the 8-byte grid
 static bool spectrum_args_ok(const void* a, const void* b, long long N, int lmax, int mmax) {

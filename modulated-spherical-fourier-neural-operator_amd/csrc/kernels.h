@@ -208,6 +208,19 @@ size_t ens_threshold_workspace_bytes(int S, int M, int nt, int nlat);
 int launch_ens_threshold_sums(const float* ens, int64_t mstride, const float* tar,
                               const float* w_lat, const float* thr, int nt, float* counts,
                               int M, int S, int nlat, int nlon, void* ws, hipStream_t s);
+// ---- pack.hip: 16-bit simple packing of selected fields, and its decode ---------------------
+// a source slab's extents, and the origin and step of the window's rows and columns
+struct PackWin {
+  int nlat, nlon, lat0, lat_step, lon0, lon_step;
+};
+// q (S_out, nlat_out, nlon_out) dense, ref and exp2 (S_out), all written whole; slab (S_out)
+// source slabs on the device or null; ws >= pack16_workspace_bytes (may hold anything)
+size_t pack16_workspace_bytes(int S_out, int nlat_out);
+int launch_pack16(const float* x, const int* slab, const PackWin& w, int S_out, int nlat_out,
+                  int nlon_out, float* ref, int* exp2, unsigned short* q, void* ws,
+                  hipStream_t s);
+int launch_unpack16(const unsigned short* q, const float* ref, const int* exp2, float* y,
+                    int64_t n, int S, hipStream_t s);
 // ---- graph.hip: the graph-convolution FiLM generator (gcn.cpp) -----------------------------
 // node-major activations (nb N, hid), hid % 4 == 0, 16-byte aligned; CSR (rp N + 1, ci, av).
 // part (gcn_partial_bytes, may hold anything on entry) receives the fixed-order column

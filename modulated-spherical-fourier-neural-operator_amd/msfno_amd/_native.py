@@ -126,6 +126,14 @@ class EnsProductsOut(ctypes.Structure):
                 ("prob", _vp)]
 
 
+class Window(ctypes.Structure):
+    """Mirror of ``msfno_window`` (include/msfno.h): the rows and columns of a slab that
+    ``msfno_pack16`` selects."""
+
+    _fields_ = [("lat0", _i), ("lat_step", _i), ("nlat_out", _i), ("lon0", _i),
+                ("lon_step", _i), ("nlon_out", _i)]
+
+
 _ip = ctypes.POINTER(_i)
 _llp = ctypes.POINTER(ctypes.c_longlong)
 
@@ -205,6 +213,10 @@ SIGNATURES = [
     ("msfno_ens_threshold_workspace_size", _sz, [_i, _i, _i, _i, _i]),
     ("msfno_ens_threshold_sums", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _i, _vp, _i, _i, _i,
                                       _i, _vp, _sz, _vp]),
+    ("msfno_pack16_workspace_size", _sz, [_i, _i, _i]),
+    ("msfno_pack16", _i, [_vp, _i, _i, _i, _vp, _i, ctypes.POINTER(Window), _vp, _vp, _vp, _vp,
+                          _sz, _vp]),
+    ("msfno_unpack16", _i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]),
     ("msfno_gcn_workspace_size", _sz, [_i, _i, _i, _i, _i, _i, _i]),
     ("msfno_gcn_forward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp, _vp, _i,
                                _i, _vp, _sz, _vp]),

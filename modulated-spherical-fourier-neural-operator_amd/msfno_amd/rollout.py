@@ -352,3 +352,24 @@ class Rollout:
                     yield i, E.products(y.contiguous().view(M, 1, C, H, W), **products_kwargs)
 
         return maps()  # the refusals above are raised by the call, not by the first next()
+
+    def export(self, x0, steps, writer, every=1, normalised_input=False):
+        """Hand every step ``i`` of ``run(x0, steps)`` where ``i % every == 0`` to
+        ``writer.put(i, y)`` (an ``export.ForecastWriter`` made for the shape of ``x0``): the
+        denormalised output is subset and packed on the device and copied to the host under
+        the following steps.  Does not flush, so that a writer can be kept across cases: call
+        ``writer.flush()`` (or leave its ``with`` block) to receive what is still in flight.
+        Returns the number of steps put."""
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.export packs whole fields; on a latitude-band rank the range of a "
+                "field spans the ranks: min / max of the rank's rows would have to be "
+                "all-reduced before the pack pass, which is not implemented")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        n = 0
+        for i, y in self.run(x0, steps, normalised_input=normalised_input):
+            if i % every == 0:
+                writer.put(i, y)
+                n += 1
+        return n
