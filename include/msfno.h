@@ -555,6 +555,57 @@ int msfno_unpack16(const unsigned short* q, const float* ref, const int* exp2, f
                    long long n_per_slab, int S, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Regridding: a separable, banded linear map over (lat, lon), optionally normalised by the
+ * valid weight: conservative remapping (WeatherBench's 1.5 degree scores and exports out of
+ * 0.25 degree), bilinear sampling, block means (the reference's SST input of the FiLM
+ * generator, coarsen(latitude=4, longitude=4, boundary='trim').mean() with NaN over land
+ * skipped, MSFNO/Models/data.py:205-213) and their adjoints (the Python mirror is
+ * msfno_amd/regrid.py: Grid, Regridder, sst_input).  x is (S_in, lat.n_in, lon.n_in) fp32 and
+ * y (S_out, lat.n_out, lon.n_out) fp32, dense, both at any 4-byte alignment.  Each axis is an
+ * ELL table on the device: start (n_out) int32, count (n_out) int32, w (n_out, taps) fp32.
+ * With cl = count cut to [0, taps] (likewise co), per output point, in fp32:
+ *     num[s][j][i] = sum_{a < cl[j]} sum_{b < co[i]} wlat[j][a] wlon[i][b] v
+ *                        x[src(s)][clamp(lat.start[j] + a, 0, lat.n_in - 1)]
+ *                                 [(lon.start[i] + b) mod lon.n_in]
+ *   Linear mode (mask == NULL and skip_nan == 0): v = 1 and y = num; min_valid and fill are
+ *   not read.  Only the taps below the count are read, padding never, so a NaN of x reaches
+ *   exactly the outputs whose counted taps cover it.
+ *   Normalised mode (a mask, skip_nan, or both): v = mask[row][col] (mask (lat.n_in,
+ *   lon.n_in) fp32 >= 0, if given) * (x == x) (if skip_nan); den is the same sum over v
+ *   alone; y = num / den where den > 0 and den >= min_valid, else fill.  Where v == 0 the
+ *   value of x is not multiplied in, so a NaN that is skipped or masked never reaches num.
+ *   The latitude index is clamped and the longitude index reduced mod lon.n_in on the device:
+ *   a wrong table gives wrong values, never a read outside a slab.  `wrap` records whether
+ *   the axis is periodic for the table's maker (the Python builders set it on the longitude);
+ *   the device does not read it.  slab (S_out) int32 on the device gives the source slab
+ *   src(s) of each output slab (any order, repeats allowed, S_out > S_in allowed; not
+ *   range-checked on the device; NULL: src(s) = s, S_out <= S_in), as in msfno_pack16.
+ *   Order of every sum: the latitude taps in index order per source column, then the
+ *   longitude taps in index order, one fused multiply-add each, the first product of a linear
+ *   chain not added to anything (one tap of weight 1 copies the bits).  No atomics and no
+ *   workspace: results are bitwise reproducible and do not depend on S, on the launch
+ *   geometry or on where a slab sits in a batch.  Every word of y is written by every call;
+ *   nothing allocates, synchronises or memsets, so the call records into a graph.
+ * MSFNO_EINVAL for null required pointers (x, y, an axis or one of its tables), an extent
+ * below 1, taps outside 1..MSFNO_REGRID_MAX_TAPS, S_out > S_in without a slab list, or a
+ * negative or non-finite min_valid; MSFNO_EUNSUPPORTED for lon.n_in > 8188 (a source row
+ * and its valid weight are staged in 64 KiB of LDS); all before any launch.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+#define MSFNO_REGRID_MAX_TAPS 32
+typedef struct msfno_regrid_axis {
+  int n_in, n_out, taps, wrap;
+  const int* start;   /* (n_out), device */
+  const int* count;   /* (n_out), device */
+  const float* w;     /* (n_out, taps), device */
+} msfno_regrid_axis;
+int msfno_regrid(const float* x, int S_in, const int* slab, int S_out,
+                 const msfno_regrid_axis* lat, const msfno_regrid_axis* lon,
+                 const float* mask /* (nlat_in, nlon_in) >= 0, or NULL */, int skip_nan,
+                 float min_valid, float fill, float* y /* (S_out, nlat_out, nlon_out) dense */,
+                 void* stream);
+
+/* ---------------------------------------------------------------------------
  * Graph-convolution FiLM generator (MSFNO/Models/gcn/gcn.py:96-167 GCN_custom,
  * layers.py:8-43 GraphConvolution; the Python mirror is msfno_amd/filmgen.py): the network
  * that turns the ocean points of an SST field into the FiLM vector, and its backward.  Per

@@ -1,5 +1,7 @@
 // libmsfno C-ABI: version, last error, and the thin validate-and-launch wrappers
-// (contractions, conv1x1, losses, verification, ensemble, spectrum).
+// (contractions, conv1x1, losses, verification, ensemble, export, regridding, spectrum).
+#include <cmath>
+
 #include "block.h"
 
 namespace msfno {
@@ -236,6 +238,30 @@ int msfno_unpack16(const unsigned short* q, const float* ref, const int* exp2, f
   MSFNO_REQUIRE(q && ref && exp2 && y && n_per_slab > 0 && S > 0, MSFNO_EINVAL,
                 "bad unpack16 arguments");
   return launch_unpack16(q, ref, exp2, y, n_per_slab, S, (hipStream_t)stream);
+}
+
+static bool regrid_axis_ok(const msfno_regrid_axis* a) {
+  return a && a->start && a->count && a->w && a->n_in >= 1 && a->n_out >= 1;
+}
+
+int msfno_regrid(const float* x, int S_in, const int* slab, int S_out,
+                 const msfno_regrid_axis* lat, const msfno_regrid_axis* lon, const float* mask,
+                 int skip_nan, float min_valid, float fill, float* y, void* stream) {
+  MSFNO_REQUIRE(x && y && S_in > 0 && S_out > 0 && regrid_axis_ok(lat) && regrid_axis_ok(lon),
+                MSFNO_EINVAL, "bad regrid arguments");
+  MSFNO_REQUIRE(lat->taps >= 1 && lat->taps <= MSFNO_REGRID_MAX_TAPS && lon->taps >= 1 &&
+                    lon->taps <= MSFNO_REGRID_MAX_TAPS,
+                MSFNO_EINVAL, "regrid: taps outside 1..32");
+  MSFNO_REQUIRE(slab || S_out <= S_in, MSFNO_EINVAL,
+                "regrid: more output slabs than slabs without a slab list");
+  MSFNO_REQUIRE(std::isfinite(min_valid) && min_valid >= 0.f, MSFNO_EINVAL,
+                "regrid: min_valid is negative or not finite");
+  MSFNO_REQUIRE(lon->n_in <= kRegridMaxLon, MSFNO_EUNSUPPORTED,
+                "regrid: source rows longer than 8188 do not fit the LDS rows");
+  const RegridAxis la = {lat->n_in, lat->n_out, lat->taps, lat->start, lat->count, lat->w};
+  const RegridAxis lo = {lon->n_in, lon->n_out, lon->taps, lon->start, lon->count, lon->w};
+  return launch_regrid(x, slab, S_out, la, lo, mask, skip_nan != 0, min_valid, fill, y,
+                       (hipStream_t)stream);
 }
 
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on

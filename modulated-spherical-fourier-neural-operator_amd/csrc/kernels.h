@@ -221,6 +221,21 @@ int launch_pack16(const float* x, const int* slab, const PackWin& w, int S_out, 
                   hipStream_t s);
 int launch_unpack16(const unsigned short* q, const float* ref, const int* exp2, float* y,
                     int64_t n, int S, hipStream_t s);
+// ---- regrid.hip: separable banded regridding (conservative, bilinear, block mean) ----------
+// one axis as an ELL table on the device: start and count (n_out), w (n_out, taps)
+struct RegridAxis {
+  int n_in, n_out, taps;
+  const int* start;
+  const int* count;
+  const float* w;
+};
+constexpr int kRegridMaxLon = 8188;  // the longest source row whose two LDS rows fit 64 KiB
+// y (S_out, lat.n_out, lon.n_out) dense, written whole; slab (S_out) source slabs on the
+// device or null; mask (lat.n_in, lon.n_in) or null.  Normalised (y = num / den where
+// den > 0 and den >= min_valid, else fill) iff a mask is given or skip_nan is set.
+int launch_regrid(const float* x, const int* slab, int S_out, const RegridAxis& lat,
+                  const RegridAxis& lon, const float* mask, bool skip_nan, float min_valid,
+                  float fill, float* y, hipStream_t s);
 // ---- graph.hip: the graph-convolution FiLM generator (gcn.cpp) -----------------------------
 // node-major activations (nb N, hid), hid % 4 == 0, 16-byte aligned; CSR (rp N + 1, ci, av).
 // part (gcn_partial_bytes, may hold anything on entry) receives the fixed-order column

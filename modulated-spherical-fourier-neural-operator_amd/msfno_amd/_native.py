@@ -134,6 +134,17 @@ class Window(ctypes.Structure):
                 ("lon_step", _i), ("nlon_out", _i)]
 
 
+REGRID_MAX_TAPS = 32
+
+
+class RegridAxis(ctypes.Structure):
+    """Mirror of ``msfno_regrid_axis`` (include/msfno.h): one axis of ``msfno_regrid`` as an
+    ELL table on the device."""
+
+    _fields_ = [("n_in", _i), ("n_out", _i), ("taps", _i), ("wrap", _i), ("start", _vp),
+                ("count", _vp), ("w", _vp)]
+
+
 _ip = ctypes.POINTER(_i)
 _llp = ctypes.POINTER(ctypes.c_longlong)
 
@@ -217,6 +228,8 @@ SIGNATURES = [
     ("msfno_pack16", _i, [_vp, _i, _i, _i, _vp, _i, ctypes.POINTER(Window), _vp, _vp, _vp, _vp,
                           _sz, _vp]),
     ("msfno_unpack16", _i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]),
+    ("msfno_regrid", _i, [_vp, _i, _vp, _i, ctypes.POINTER(RegridAxis),
+                          ctypes.POINTER(RegridAxis), _vp, _i, _f, _f, _vp, _vp]),
     ("msfno_gcn_workspace_size", _sz, [_i, _i, _i, _i, _i, _i, _i]),
     ("msfno_gcn_forward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp, _vp, _i,
                                _i, _vp, _sz, _vp]),

@@ -117,8 +117,9 @@ class Resolved:
 class Selection:
     """What of a (B, C, H, W) field is exported: ``channels`` (None for all, a slice, or a
     sequence of channel indices in any order, repeats allowed), and ``lat`` / ``lon`` (a slice
-    with a step >= 1, or one index).  WeatherBench's 1.5 degree grid out of 0.25 degree is
-    ``Selection(lat=slice(None, None, 6), lon=slice(None, None, 6))``.  ``resolve(shape)``
+    with a step >= 1, or one index).  ``Selection(lat=slice(None, None, 6), lon=slice(None,
+    None, 6))`` takes the 0.25 degree field at the nodes of the 1.5 degree grid: a point
+    sample; the cell mean is ``regrid.Regridder`` (``Rollout.export(regrid=)``).  ``resolve(shape)``
     raises ``ValueError`` for a selection that is empty or leaves the field."""
 
     def __init__(self, channels=None, lat=slice(None), lon=slice(None)):

@@ -132,6 +132,14 @@ def load_filmed_checkpoint(model, checkpoint, film_checkpoint=None, retrain_film
     return model, strict
 
 
+def _whole_fields_only(model, regrid):
+    if regrid is not None and getattr(model, "world", 1) > 1:
+        raise NotImplementedError(
+            "regrid= maps whole fields; on a latitude-band rank the rows of a destination "
+            "cell's band lie on the neighbouring ranks too, and band-sharded regridding is "
+            "not implemented")
+
+
 class Rollout:
     """On-device autoregressive stepping of a FourierNeuralOperatorNet[_Filmed], or
     of one rank's ``LatBandNet`` (the multi-GPU form of config 5: every rank steps
@@ -243,7 +251,7 @@ class Rollout:
                 yield i, self.normalise(x, reverse=True)
 
     def verify(self, x0, truths, steps, every=1, weights="uniform", normalised_input=False,
-               verifier=None):
+               verifier=None, regrid=None):
         """Score a rollout on the device (model.py:737-758, train.py:533-583 without the
         per-step copy to the host): ``run(x0, steps)`` with every step ``i`` where
         ``i % every == 0`` (``every = validation_step_skip + 1``, train.py:551) scored
@@ -252,8 +260,12 @@ class Rollout:
         (host tensors are copied without blocking).  Returns ``verification.Scores`` of
         (n_scored, B, C) tensors under ``weights`` (``verification.Verifier``).  Pass a
         ``verifier`` of your own to keep the raw sums (``verifier.sums``) or to reuse its
-        buffers; its weights then apply."""
+        buffers; its weights then apply.  With ``regrid`` (a ``regrid.Regridder`` from the
+        model's grid) every scored output goes through it first: truths are then given on the
+        destination grid, the default verifier is built for the destination shape and a
+        ``weights`` name means the destination grid's latitudes."""
         from . import verification as V
+        _whole_fields_only(self.model, regrid)
         if getattr(self.model, "world", 1) > 1:
             raise NotImplementedError(
                 "Rollout.verify scores whole fields; on a latitude-band rank call "
@@ -265,6 +277,8 @@ class Rollout:
         n_scored = (steps + every - 1) // every
         if verifier is None:
             B, C, H, W = x0.shape
+            if regrid is not None:
+                H, W = regrid.out_shape
             verifier = V.Verifier(weights, H, W, n_scored, B, C, device=x0.device)
         elif verifier.sums.shape[0] < n_scored:
             raise ValueError(f"verifier has {verifier.sums.shape[0]} slots, {n_scored} needed")
@@ -279,11 +293,11 @@ class Rollout:
                                  "one item each") from None
             if isinstance(item, torch.Tensor):
                 item = (item,)
-            verifier.update(i // every, y, *item)
+            verifier.update(i // every, y if regrid is None else regrid(y), *item)
         return verifier.scores()
 
     def verify_ensemble(self, x0, truths, steps, every=1, weights="uniform",
-                        normalised_input=False, verifier=None):
+                        normalised_input=False, verifier=None, regrid=None):
         """Score an ensemble rollout on the device: the batch of ``x0`` (M, C, H, W) is the
         M members of one case (``self.film`` may differ per member), stepped together by
         ``run(x0, steps)``; every step ``i`` where ``i % every == 0`` is scored against the
@@ -292,8 +306,11 @@ class Rollout:
         viewed as (M, 1, C, H, W) without a copy.  Returns ``ensemble.EnsembleScores`` of
         (n_scored, 1, C) tensors and the (n_scored, 1, C, M + 1) rank histograms under
         ``weights`` (``ensemble.EnsembleVerifier``).  Pass a ``verifier`` of your own (built
-        with B = 1) to keep the raw sums or to reuse its buffers; its weights then apply."""
+        with B = 1) to keep the raw sums or to reuse its buffers; its weights then apply.
+        ``regrid`` as in ``verify``: the members are regridded before they are scored, and
+        truths, verifier and weights are those of the destination grid."""
         from . import ensemble as E
+        _whole_fields_only(self.model, regrid)
         if getattr(self.model, "world", 1) > 1:
             raise NotImplementedError(
                 "Rollout.verify_ensemble scores whole fields; on a latitude-band rank call "
@@ -305,6 +322,8 @@ class Rollout:
         if x0.dim() != 4:
             raise ValueError(f"x0 must be (M, C, H, W), got {tuple(x0.shape)}")
         M, C, H, W = x0.shape
+        if regrid is not None:
+            H, W = regrid.out_shape
         n_scored = (steps + every - 1) // every
         if verifier is None:
             verifier = E.EnsembleVerifier(weights, H, W, n_scored, M, 1, C, device=x0.device)
@@ -322,6 +341,8 @@ class Rollout:
             if tuple(tar.shape) not in ((C, H, W), (1, C, H, W)):
                 raise ValueError(f"a truth must be (C, H, W) or (1, C, H, W) = {(C, H, W)}, "
                                  f"got {tuple(tar.shape)}")
+            if regrid is not None:
+                y = regrid(y)
             verifier.update(i // every, y.contiguous().view(M, 1, C, H, W),
                             tar.reshape(1, C, H, W))
         return verifier.scores()
@@ -353,13 +374,16 @@ class Rollout:
 
         return maps()  # the refusals above are raised by the call, not by the first next()
 
-    def export(self, x0, steps, writer, every=1, normalised_input=False):
+    def export(self, x0, steps, writer, every=1, normalised_input=False, regrid=None):
         """Hand every step ``i`` of ``run(x0, steps)`` where ``i % every == 0`` to
         ``writer.put(i, y)`` (an ``export.ForecastWriter`` made for the shape of ``x0``): the
         denormalised output is subset and packed on the device and copied to the host under
         the following steps.  Does not flush, so that a writer can be kept across cases: call
         ``writer.flush()`` (or leave its ``with`` block) to receive what is still in flight.
+        With ``regrid`` (a ``regrid.Regridder`` from the model's grid) the writer is one made
+        for the destination shape and receives the regridded field.
         Returns the number of steps put."""
+        _whole_fields_only(self.model, regrid)
         if getattr(self.model, "world", 1) > 1:
             raise NotImplementedError(
                 "Rollout.export packs whole fields; on a latitude-band rank the range of a "
@@ -370,6 +394,6 @@ class Rollout:
         n = 0
         for i, y in self.run(x0, steps, normalised_input=normalised_input):
             if i % every == 0:
-                writer.put(i, y)
+                writer.put(i, y if regrid is None else regrid(y))
                 n += 1
         return n
