@@ -417,6 +417,40 @@ int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, co
                       int nlon, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Regional and masked verification: the sums of msfno_verify_sums per region, for
+ * 1 <= nregions <= 32 regions of the grid in one call (the Python mirror is
+ * msfno_amd/regions.py and verification.region_sums).  Bit r of three device uint32 tables
+ * speaks for region r: pixel (h, x) is in region r iff bit r of
+ *   row_bits[h] & col_bits[x] & pix_bits[h * nlon + x]
+ * is set (row_bits (nlat), col_bits (nlon), pix_bits (nlat, nlon) or NULL for all ones;
+ * bits at and above nregions are ignored).  Membership is binary.  A pixel is valid unless
+ * skip_nan != 0 and tar is NaN there, or the slab has a climatology and clim is NaN there;
+ * a NaN in prd is never skipped.  Per (bc, region), over the region's valid pixels,
+ *   sums[bc][r] = { n = sum w, se, err, ae, pa2, ta2, cross }
+ * with the last six as in msfno_verify_sums; the scores divide by n, not by nlon sum(w).
+ * Out-of-region and skipped pixels are selected out, never multiplied by zero: a region's
+ * sums depend only on the values at its own valid pixels (a NaN or Inf elsewhere leaves
+ * them bit-identical); a region of all ones with skip_nan = 0 has bitwise the six sums of
+ * msfno_verify_sums on the same inputs; a missing truth and a cleared pix_bits bit give
+ * the same bits; an empty or all-missing region gives seven +0.  A latitude band passes its
+ * own rows of every field, of w_lat, row_bits and pix_bits; the sums of the bands add up.
+ * Deterministic as msfno_verify_sums (no atomics, fixed order); every word of sums is
+ * written by every call; the workspace may hold anything on entry; nothing allocates,
+ * synchronises or memsets, so the call records into a graph.  MSFNO_EINVAL for null
+ * required pointers (pix_bits may be NULL), nregions outside 1..32, an extent below 1, or
+ * only one of clim / clim_slab; MSFNO_EWORKSPACE for a short workspace; both before any
+ * launch.  The workspace size is 0 for arguments the call refuses.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+size_t msfno_verify_regions_workspace_size(int BC, int nlat, int nlon, int nregions);
+int msfno_verify_region_sums(const float* prd, const float* tar, const float* w_lat,
+                             const float* clim, const int* clim_slab,
+                             const uint32_t* row_bits, const uint32_t* col_bits,
+                             const uint32_t* pix_bits /* or NULL */, int nregions, int skip_nan,
+                             float* sums /* (BC, nregions, 7) */, int BC, int nlat, int nlon,
+                             void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Ensemble verification and the (fair) CRPS: the sums behind the ensemble-mean RMSE and
  * bias, the MAE, the spread, the spread/skill ratio, the CRPS, the fair CRPS and the rank
  * histogram of M members against one truth (the reference has no ensemble score; the

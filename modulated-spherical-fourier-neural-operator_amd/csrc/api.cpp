@@ -115,6 +115,30 @@ int msfno_verify_sums(const float* prd, const float* tar, const float* w_lat, co
                             (hipStream_t)stream);
 }
 
+size_t msfno_verify_regions_workspace_size(int BC, int nlat, int nlon, int nregions) {
+  if (BC <= 0 || nlat <= 0 || nlon <= 0 || nregions < 1 || nregions > 32) return 0;
+  return verify_regions_workspace_bytes(BC, nlat, nlon, nregions);
+}
+
+int msfno_verify_region_sums(const float* prd, const float* tar, const float* w_lat,
+                             const float* clim, const int* clim_slab, const uint32_t* row_bits,
+                             const uint32_t* col_bits, const uint32_t* pix_bits, int nregions,
+                             int skip_nan, float* sums, int BC, int nlat, int nlon, void* ws,
+                             size_t ws_bytes, void* stream) {
+  MSFNO_REQUIRE(prd && tar && w_lat && row_bits && col_bits && sums && ws && BC > 0 &&
+                    nlat > 0 && nlon > 0,
+                MSFNO_EINVAL, "bad verify_region_sums arguments");
+  MSFNO_REQUIRE(nregions >= 1 && nregions <= 32, MSFNO_EINVAL,
+                "verify_region_sums: nregions must be in 1..32");
+  MSFNO_REQUIRE((clim == nullptr) == (clim_slab == nullptr), MSFNO_EINVAL,
+                "verify_region_sums: clim and clim_slab must both be set or both be null");
+  MSFNO_REQUIRE(ws_bytes >= msfno_verify_regions_workspace_size(BC, nlat, nlon, nregions),
+                MSFNO_EWORKSPACE, "verify_region_sums: workspace too small");
+  return launch_verify_region_sums(prd, tar, w_lat, clim, clim_slab, row_bits, col_bits, pix_bits,
+                                   nregions, skip_nan, sums, BC, nlat, nlon, ws,
+                                   (hipStream_t)stream);
+}
+
 size_t msfno_ens_workspace_size(int S, int M, int nlat, int nlon) {
   if (S <= 0 || M < 2 || M > 32 || nlat <= 0 || nlon <= 0) return 0;
   return ens_workspace_bytes(S, M, nlat, nlon);

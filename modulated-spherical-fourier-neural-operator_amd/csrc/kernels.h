@@ -175,6 +175,17 @@ size_t verify_workspace_bytes(int BC, int nlat, int nlon);
 int launch_verify_sums(const float* prd, const float* tar, const float* w_lat, const float* clim,
                        const int* clim_slab, float* sums, int BC, int nlat, int nlon, void* ws,
                        hipStream_t s);
+// ---- verify_regions.hip: the verification sums per region -----------------------------------
+// sums[bc][r] = {n, se, err, ae, pa2, ta2, cross} over the valid pixels of region r: bit r of
+// row_bits[h] & col_bits[x] & pix_bits[h][x] (pix_bits may be null: all ones), 1 <= nregions
+// <= 32; skip_nan drops the pixels whose truth (or climatology, where the slab has one) is
+// NaN; ws >= verify_regions_workspace_bytes (may hold anything on entry)
+size_t verify_regions_workspace_bytes(int BC, int nlat, int nlon, int nregions);
+int launch_verify_region_sums(const float* prd, const float* tar, const float* w_lat,
+                              const float* clim, const int* clim_slab, const uint32_t* row_bits,
+                              const uint32_t* col_bits, const uint32_t* pix_bits, int nregions,
+                              int skip_nan, float* sums, int BC, int nlat, int nlon, void* ws,
+                              hipStream_t s);
 // ---- ensemble.hip: ensemble verification sums and the CRPS gradient -------------------------
 // member i of slab s at ens + i * mstride + s * nlat * nlon (mstride in floats);
 // sums[s] = {se, err, abs, gini, sq}, hist[s][0..M] the weighted rank counts or null (see

@@ -214,6 +214,9 @@ SIGNATURES = [
     ("msfno_loss_backward", _i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     ("msfno_verify_workspace_size", _sz, [_i, _i, _i]),
     ("msfno_verify_sums", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    ("msfno_verify_regions_workspace_size", _sz, [_i, _i, _i, _i]),
+    ("msfno_verify_region_sums", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i,
+                                      _i, _vp, _sz, _vp]),
     ("msfno_ens_workspace_size", _sz, [_i, _i, _i, _i]),
     ("msfno_ens_sums", _i, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz,
                             _vp]),

@@ -251,7 +251,7 @@ class Rollout:
                 yield i, self.normalise(x, reverse=True)
 
     def verify(self, x0, truths, steps, every=1, weights="uniform", normalised_input=False,
-               verifier=None, regrid=None):
+               verifier=None, regrid=None, regions=None, skip_nan=False):
         """Score a rollout on the device (model.py:737-758, train.py:533-583 without the
         per-step copy to the host): ``run(x0, steps)`` with every step ``i`` where
         ``i % every == 0`` (``every = validation_step_skip + 1``, train.py:551) scored
@@ -263,7 +263,11 @@ class Rollout:
         buffers; its weights then apply.  With ``regrid`` (a ``regrid.Regridder`` from the
         model's grid) every scored output goes through it first: truths are then given on the
         destination grid, the default verifier is built for the destination shape and a
-        ``weights`` name means the destination grid's latitudes."""
+        ``weights`` name means the destination grid's latitudes.  With ``regions`` (a
+        ``regions.Regions`` of the scored grid: the destination grid under ``regrid``) the
+        default verifier is a ``verification.RegionalVerifier`` and the scores are
+        (n_scored, B, C, R), one column per region; ``skip_nan`` then leaves out the pixels
+        whose truth or climatology is NaN."""
         from . import verification as V
         _whole_fields_only(self.model, regrid)
         if getattr(self.model, "world", 1) > 1:
@@ -271,14 +275,29 @@ class Rollout:
                 "Rollout.verify scores whole fields; on a latitude-band rank call "
                 "verification.field_sums on the rank's rows with w[rows] and "
                 "clim[..., rows, :], all-reduce the (B, C, 6) sums over the ranks, then "
-                "verification.finish with the whole grid's w")
+                "verification.finish with the whole grid's w; for regions, "
+                "verification.region_sums with regions.rows(rows), all-reduce the "
+                "(B, C, R, 7) sums, then verification.finish_regions")
         if steps < 1 or every < 1:
             raise ValueError("steps and every must be >= 1")
+        if skip_nan and regions is None and verifier is None:
+            raise ValueError("skip_nan needs regions (regions.Regions.boxes(grid, {'global': "
+                             "(None, None, None, None)}) for the whole grid)")
         n_scored = (steps + every - 1) // every
-        if verifier is None:
-            B, C, H, W = x0.shape
-            if regrid is not None:
-                H, W = regrid.out_shape
+        B, C, H, W = x0.shape
+        if regrid is not None:
+            H, W = regrid.out_shape
+        if regions is not None:
+            if tuple(getattr(regions, "shape", ())) != (H, W):
+                raise ValueError(f"the regions are of a {getattr(regions, 'shape', None)} grid, "
+                                 f"the scored fields are {(H, W)}")
+            if verifier is not None and getattr(verifier, "regions", None) is not regions:
+                raise ValueError("pass regions or a verifier built on them, not two that "
+                                 "differ")
+        if verifier is None and regions is not None:
+            verifier = V.RegionalVerifier(weights, regions, n_scored, B, C, skip_nan=skip_nan,
+                                          device=x0.device)
+        elif verifier is None:
             verifier = V.Verifier(weights, H, W, n_scored, B, C, device=x0.device)
         elif verifier.sums.shape[0] < n_scored:
             raise ValueError(f"verifier has {verifier.sums.shape[0]} slots, {n_scored} needed")

@@ -18,6 +18,12 @@ the whole grid's ``w``.
 
 ``Verifier`` is the preallocated form for a rollout (one launch per scored step into a
 slot, nothing synchronises); ``Rollout.verify`` drives it.
+
+Regional and masked scores: ``region_sums`` (``msfno_verify_region_sums``,
+csrc/verify_regions.hip) takes a ``regions.Regions`` and leaves seven sums per (batch,
+channel, region), ``n = sum w`` over the region's valid pixels and the six above over the
+same pixels; ``finish_regions`` divides by that ``n``.  With ``skip_nan`` a pixel whose truth
+(or climatology) is NaN is left out.  ``RegionalVerifier`` is the rollout form.
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ from . import _native as N
 
 NSUMS = 6
 SE, ERR, AE, PA2, TA2, CROSS = range(NSUMS)
+NRSUMS = 7   # per region: n, then the six
 
 Scores = namedtuple("Scores", ["mse", "rmse", "bias", "mae", "skill", "acc"])
 
@@ -152,6 +159,77 @@ def finish(sums, w, nlon, batch_mean=False) -> Scores:
     return Scores(mse, torch.sqrt(mse), err / n, ae / n, skill, acc)
 
 
+def regions_workspace(B: int, C: int, nlat: int, nlon: int, nregions: int, device) -> torch.Tensor:
+    """A workspace for ``msfno_verify_region_sums`` at this shape (contents do not matter)."""
+    return torch.empty(N.lib().msfno_verify_regions_workspace_size(B * C, nlat, nlon, nregions),
+                       dtype=torch.uint8, device=device)
+
+
+def _check_regions(regions, shape):
+    from .regions import Regions
+    if not isinstance(regions, Regions):
+        raise ValueError(f"regions must be a regions.Regions, got {type(regions).__name__}")
+    if tuple(regions.shape) != tuple(shape[2:]):
+        raise ValueError(f"the regions are of a {regions.shape} grid, the fields are "
+                         f"{tuple(shape[2:])}")
+    return regions
+
+
+@N.on_input_device
+def _launch_regions(prd, tar, w, clim, clim_slab, regions, skip_nan, out, ws):
+    B, C, H, W = prd.shape
+    row, col, pix = regions.tables(prd.device)
+    N.check(N.lib().msfno_verify_region_sums(
+        prd.data_ptr(), tar.data_ptr(), w.data_ptr(), N.ptr(clim), N.ptr(clim_slab),
+        row.data_ptr(), col.data_ptr(), N.ptr(pix), len(regions), int(bool(skip_nan)),
+        out.data_ptr(), B * C, H, W, ws.data_ptr(), ws.numel(), N.stream_of(prd.device)),
+        "msfno_verify_region_sums")
+    return out
+
+
+@torch.no_grad()
+def region_sums(prd, tar, w, regions, clim=None, clim_slab=None, skip_nan=False) -> torch.Tensor:
+    """(B, C, R, 7) fp32 = {n, se, err, ae, pa2, ta2, cross} per region of ``regions`` (a
+    ``regions.Regions`` of the fields' grid): ``n = sum w`` over the region's valid pixels
+    and the six sums of ``field_sums`` over the same pixels.  Fields, ``w``, ``clim`` and
+    ``clim_slab`` as in ``field_sums``.  With ``skip_nan`` a pixel is left out where ``tar``
+    is NaN or, for a slab with a climatology, ``clim`` is; a NaN in ``prd`` is never
+    skipped.  A region's sums depend only on the values at its own valid pixels.  No
+    gradient."""
+    prd, tar, w = _check_fields(prd, tar, w)
+    regions = _check_regions(regions, prd.shape)
+    clim, clim_slab = _check_clim(clim, clim_slab, prd.shape, prd.device)
+    B, C, H, W = prd.shape
+    R = len(regions)
+    out = torch.empty(B, C, R, NRSUMS, dtype=torch.float32, device=prd.device)
+    return _launch_regions(prd, tar, w, clim, clim_slab, regions, skip_nan, out,
+                           regions_workspace(B, C, H, W, R, prd.device))
+
+
+def finish_regions(sums, batch_mean=False) -> Scores:
+    """Scores from (..., B, C, R, 7) regional sums (device or host, any float dtype), each
+    of shape (..., B, C, R): as ``finish`` with the region's own ``n`` (the first of its
+    seven sums) in place of ``nlon * sum(w)``.  Every score of a region with ``n == 0``
+    (empty, or all of it missing) is NaN; ``skill`` and ``acc`` are NaN too where the slab
+    had no climatology.  ``batch_mean`` adds the sums over B first and returns (..., C, R)."""
+    if sums.shape[-1] != NRSUMS or sums.dim() < 4:
+        raise ValueError(f"sums must be (..., B, C, R, {NRSUMS}), got {tuple(sums.shape)}")
+    if batch_mean:
+        sums = sums.sum(dim=-4)
+    n, se, err, ae, pa2, ta2, cross = sums.unbind(-1)
+    nan = torch.full_like(se, float("nan"))
+    empty = n == 0
+
+    def per_n(x):
+        return torch.where(empty, nan, x / n)
+
+    mse = per_n(se)
+    none = empty | ((pa2 == 0) & (ta2 == 0))
+    skill = torch.where(none, nan, 1 - se / ta2)
+    acc = torch.where(none, nan, cross / (torch.sqrt(pa2) * torch.sqrt(ta2)))
+    return Scores(mse, torch.sqrt(mse), per_n(err), per_n(ae), skill, acc)
+
+
 def mse_normalised(mse, stds):
     """The MSE in normalised space from the raw-space ``mse`` (..., C): mse / std^2, exact
     because the reference's normalisation is a per-channel affine (model.py:273-279)."""
@@ -205,3 +283,40 @@ class Verifier(F.SlotVerifier):
     def scores(self, batch_mean=False) -> Scores:
         """``finish`` of all slots: Scores of (n_scored, B, C) tensors, or (n_scored, C)."""
         return finish(self.sums, self.w, self.shape[3], batch_mean=batch_mean)
+
+
+class RegionalVerifier(F.SlotVerifier):
+    """``Verifier`` per region: the sums of ``n_scored`` scored steps of a rollout of
+    (B, C, nlat, nlon) fields over the R regions of ``regions`` (a ``regions.Regions`` of
+    that grid), in one preallocated (n_scored, B, C, R, 7) device tensor ``sums`` with one
+    workspace.  ``skip_nan`` as in ``region_sums``.  ``update`` launches into a slot and
+    never synchronises, so it records into a graph; a slot that was never updated holds
+    NaN."""
+
+    def __init__(self, weights, regions, n_scored, B, C, skip_nan=False, device="cuda"):
+        from .regions import Regions
+        if not isinstance(regions, Regions):
+            raise ValueError(f"regions must be a regions.Regions, got {type(regions).__name__}")
+        nlat, nlon = regions.shape
+        super().__init__(weights, nlat, nlon, n_scored, B, C, device)
+        self.shape = (B, C, nlat, nlon)
+        self.regions, self.skip_nan = regions, bool(skip_nan)
+        self.sums = torch.full((n_scored, B, C, len(regions), NRSUMS), float("nan"),
+                               dtype=torch.float32, device=self.device)
+        self._ws = regions_workspace(B, C, nlat, nlon, len(regions), self.device)
+        regions.tables(self.device)
+
+    @torch.no_grad()
+    def update(self, k, y, tar, clim=None, clim_slab=None):
+        """Score the forecast ``y`` against ``tar`` (and ``clim``, as in ``region_sums``)
+        into slot ``k``.  A host ``tar`` or ``clim`` is copied with non_blocking=True."""
+        self._check_slot(k, y, "fields")
+        y, tar, w = _check_fields(y, self._on_device(tar), self.w)
+        clim, clim_slab = _check_clim(self._on_device(clim), clim_slab, y.shape, y.device)
+        _launch_regions(y, tar, w, clim, clim_slab, self.regions, self.skip_nan, self.sums[k],
+                        self._ws)
+
+    def scores(self, batch_mean=False) -> Scores:
+        """``finish_regions`` of all slots: Scores of (n_scored, B, C, R) tensors, or
+        (n_scored, C, R)."""
+        return finish_regions(self.sums, batch_mean=batch_mean)
