@@ -384,65 +384,37 @@ int msfno_band_block_stage(const msfno_block_desc* d, msfno_band_plan_t p, int s
   carve_band(cv, b, d, p, B);
   const int64_t C = d->C, BC = (int64_t)B * C, R = 2 * BC;
   const int64_t Pout = (int64_t)p->rows_out * p->nlon_out;
-  // the skip GEMM as in msfno_block_forward: on x planes written by the rfft (forked
-  // after it) when the plane buffer exists, on fp32 x on the x3h engine (forked in
-  // stage 1 once the global statistics give its scales: the unsharded block's scales,
-  // so both round alike), else on fp32 x (forked first)
-  const bool xpl = skip_planes(d, p->fwd, b.fb);
-  const int64_t Pl = (int64_t)p->rows_in * p->nlon_in;
-  auto launch_skip = [&]() -> int {
+  // the inner skip as in msfno_block_forward (skip_fork_point), launched by the stage its
+  // fork point falls into.  The x3h skip is forked in stage 1 for both filters, once the
+  // global statistics give its scales (the unsharded block's, so both round alike): the
+  // block's late fork of the linear filter would fall into stage 2, which a rank that owns
+  // no zonal wavenumber leaves at once, and is not measured here
+  SkipFork at = skip_fork_point(d, p->fwd, b.fb, false);
+  if (at == SKIP_BEFORE_INV) at = SKIP_AFTER_NORM0;
+  auto fork_skip = [&]() -> int {
+    // The skip joins on the slot's event, not the side context's: the stages are separate
+    // calls and the pipelined sub-batches interleave.  They put this side-stream skip beside
+    // other sub-batches' row FFTs: safe since the FFT units carry no packed-FP32
+    // op_sel:[0,1] forms.  launch_skip_h on its stand-alone grid (2 per CU)
     std::shared_ptr<SideCtx> side;
     MSFNO_TRY(side_ctx(&side, s));
-    hipStream_t ss = s;
-    hipEvent_t join = side ? slot_event(p, io->slot) : nullptr;
-    MSFNO_REQUIRE(!side || join, MSFNO_EHIP, "band slot event unavailable (slot must be 0..63)");
-    if (side) {
-      MSFNO_CHECK_HIP(hipEventRecord(side->fork, s));
-      MSFNO_CHECK_HIP(hipStreamWaitEvent(side->side, side->fork, 0));
-      ss = side->side;
-    }
-    prof(ST_SKIP, ss);
-    GemmEpi e;
-    e.bias = d->skip_b;
-    // x3h: B-row scales from the global norm0 statistics (stage 1).  The pipelined
-    // sub-batches put this side-stream skip beside other sub-batches' row FFTs: safe since
-    // the FFT units carry no packed-FP32 op_sel:[0,1] forms
-    if (b.fb.xs && C == 256 && skip_h_env()) {
-      MSFNO_TRY(launch_skip_h(d->skip_w, b.fb.xs, io->x, b.x1, d->skip_b, B, Pl, b.fb.dw.skip,
-                              b.fb.dw.skip_b, ss));
-    } else if (b.fb.xs) {
-      MSFNO_TRY(gemm_x3(d->skip_w, (int)C, b.fb.xs, io->x, b.x1, (int)C, (int)Pl, (int)C,
-                        (int)Pl, (int)Pl, C * Pl, C * Pl, B, e, b.fb.dw.skip, b.fb.dw.skip_b,
-                        ss));
-    } else if (xpl) {
-      e.b_planes = b.fb.x1p;
-      e.b_plane_stride = C * Pl;
-      MSFNO_TRY(gemm_x6p(d->skip_w, b.x1, (int)C, (int)Pl, (int)C, (int)C, (int)Pl, (int)Pl,
-                         0, 3 * C * Pl, C * Pl, B, e, b.fb.dw.skip, b.fb.dw.skip_b, ss));
-    } else {
-      MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, io->x, b.x1, (int)C, (int)Pl,
-                           (int)C, (int)C, (int)Pl, (int)Pl, 0, C * Pl, C * Pl, B, e,
-                           b.fb.dw.skip, b.fb.dw.skip_b, ss));
-    }
-    if (side) {
-      prof(ST_END, ss);
-      MSFNO_CHECK_HIP(hipEventRecord(join, ss));
-    }
-    return MSFNO_OK;
+    InnerSkip k{d, &b.fb, io->x, b.x1, B, (int64_t)p->rows_in * p->nlon_in, at};
+    k.side = side.get();
+    k.join = side ? slot_event(p, io->slot) : nullptr;
+    MSFNO_REQUIRE(!side || k.join, MSFNO_EHIP, "band slot event unavailable (slot must be 0..63)");
+    return skip_fork(k, s);
   };
   switch (stage) {
     case 0: {
       MSFNO_REQUIRE(io->x && io->stats_local, MSFNO_EINVAL, "stage 0 needs x and stats_local");
-      if (d->inner_skip == MSFNO_SKIP_LINEAR) {
-        MSFNO_REQUIRE(d->skip_w, MSFNO_EINVAL, "missing inner_skip weight");
-        if (!xpl && !b.fb.xs) MSFNO_TRY(launch_skip());
-      }
+      if (at != SKIP_NONE) MSFNO_REQUIRE(d->skip_w, MSFNO_EINVAL, "missing inner_skip weight");
+      if (at == SKIP_FIRST) MSFNO_TRY(fork_skip());
       prof(ST_FFT_FWD, s);
       const float scale = (float)(2.0 * M_PI / p->nlon_in);
       const C2RPlanes xp{b.fb.x1p, (int)C, p->rows_in};
       MSFNO_TRY(launch_fft_r2c_rows(p->fwd->fft, io->x, b.Xn, b.rs, BC * p->rows_in, p->mmax,
-                                    scale, s, xpl ? &xp : nullptr));
-      if (xpl) MSFNO_TRY(launch_skip());
+                                    scale, s, at == SKIP_AFTER_FFT ? &xp : nullptr));
+      if (at == SKIP_AFTER_FFT) MSFNO_TRY(fork_skip());
       prof(ST_NORM0, s);
       MSFNO_TRY(launch_stats_partial(b.rs, p->rows_in, p->nlon_in, BC, io->stats_local, s));
       prof(ST_END, s);
@@ -454,9 +426,9 @@ int msfno_band_block_stage(const msfno_block_desc* d, msfno_band_plan_t p, int s
       MSFNO_TRY(launch_chan_affine_parts(io->stats_all, p->world, B, (int)C, d->norm0_w,
                                          d->norm0_b, d->norm_eps, nullptr, nullptr, 0.f, b.sc0,
                                          b.sh0, s, b.fb.xs, nullptr, b.fb.lsig));
-      if (b.fb.xs && d->inner_skip == MSFNO_SKIP_LINEAR) {
+      if (at == SKIP_AFTER_NORM0) {
         MSFNO_REQUIRE(io->x && d->skip_w, MSFNO_EINVAL, "stage 1 needs x for the x3h skip");
-        MSFNO_TRY(launch_skip());
+        MSFNO_TRY(fork_skip());
       }
       prof(ST_BAND_PACK, s);
       const BandRows o = band_rows(p->nlat_in, p->row_in.data(), p->rank);
@@ -480,7 +452,7 @@ int msfno_band_block_stage(const msfno_block_desc* d, msfno_band_plan_t p, int s
                                    b.fb.isr, b.fb.Sa, (int)R, s));
       else
         MSFNO_TRY(legendre_fwd(p->fwd, io->recv, b.fb.Sa, (int)R, s));
-      MSFNO_TRY(run_filter(d, p->fwd, p->inv, b.fb, B, s));
+      MSFNO_TRY(run_filter(d, p->fwd, b.fb, B, s));
       prof(ST_LEG_INV, s);
       MSFNO_TRY(legendre_inv(p->inv, b.fb.Sa, io->send, (int)R, s));
       prof(ST_END, s);

@@ -2,7 +2,6 @@
 // block_fwd.cpp (single-GPU block), block_bwd.cpp, band.cpp (latitude-band sharded block),
 // mlp.cpp, profile.cpp.  Not part of the C-ABI.
 #pragma once
-#include <functional>
 #include <memory>
 #include "kernels.h"
 
@@ -94,19 +93,45 @@ bool x3f_env();
 bool x3f_usable(msfno_sht_plan_s* f);
 int legendre_fwd_x3f(msfno_sht_plan_s* f, const unsigned short* Xp, const float* isr, float* S,
                      int R, hipStream_t s);
-// spectral filter on S (f->spec layout) in b.Sa (in place)
-int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
-               const BlockBufs& b, int B, hipStream_t s);
-// x -> (FFT, norm0 folded) -> Legendre -> filter -> inverse Legendre -> Yn
-// xplanes: the forward FFT also writes x as bf16x3 planes; after_fft runs once the
-// forward FFT is enqueued (the block forks its inner-skip GEMM there)
+// spectral filter on S (f->spec layout) in b.Sa (in place): one chain per engine
+int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, const BlockBufs& b, int B,
+               hipStream_t s);
+
+// ---- the inner skip x1 = Ws·sx + bs (inner_skip = linear) of the block and the band ----
+// where the skip GEMM is launched in the forward's stream order (skip_fork_point)
+enum SkipFork {
+  SKIP_NONE,         // no linear inner skip: nothing to launch
+  SKIP_FIRST,        // before the forward FFT
+  SKIP_AFTER_FFT,    // the forward FFT writes x as bf16x3 planes into b.x1p: the GEMM's B operand
+  SKIP_AFTER_NORM0,  // the norm0 statistics give the x3h B-row scales b.xs
+  SKIP_BEFORE_INV    // after the filter, before the inverse Legendre
+};
+// separate_input: the skip reads another tensor than the filter (global_conv's residual)
+SkipFork skip_fork_point(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b,
+                         bool separate_input);
+// one skip launch: operands, fork point, and what differs between the callers
+struct InnerSkip {
+  const msfno_block_desc* d;
+  const BlockBufs* b;  // xs, x1p, dw.skip / dw.skip_b
+  const float* sx;     // (B, C, P) skip input
+  float* x1;           // (B, C, P) destination
+  int B;
+  int64_t P;
+  SkipFork at;
+  bool own_scales = false;  // x3h: b->xs from the maximum of sx first (no norm0 statistics)
+  bool quarter_cu = false;  // launch_skip_h's side grid (kernels.h)
+  SideCtx* side = nullptr;  // fork to side->side and record `join` there; null: in line on s
+  hipEvent_t join = nullptr;
+};
+// fork from s to k.side, the skip GEMM (block_fwd.cpp: skip_gemm, the only engine dispatch),
+// record k.join; the caller waits for k.join on s before it reads x1
+int skip_fork(const InnerSkip& k, hipStream_t s);
+
+// x -> (FFT, norm0 folded) -> Legendre -> filter -> inverse Legendre -> Yn.  skip (or null:
+// msfno_filter_forward, the FiLM backward's recompute) is forked at skip->at
 int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
                  const BlockBufs& b, const float* x, int B, bool norm0, hipStream_t s,
-                 const C2RPlanes* xplanes = nullptr,
-                 const std::function<int()>& after_fft = std::function<int()>(),
-                 const std::function<int()>& after_norm0 = std::function<int()>(),
-                 const std::function<int()>& after_leg = std::function<int()>(),
-                 const std::function<int()>& before_inv = std::function<int()>());
+                 const InnerSkip* skip = nullptr);
 // Yt -> spatial rows; out = act(addsrc + irfft)
 int run_inverse_fft(msfno_sht_plan_s* g, const BlockBufs& b, int B, int C, float* out,
                     const float* addsrc, float2* rowstats, int act, hipStream_t s,
@@ -134,8 +159,7 @@ int run_block_mlp(const msfno_block_desc* d, const float* x1, const unsigned sho
                   const DenseWs& dw, hipStream_t s);
 int64_t mlp_h_floats(int B, int64_t Hd, int64_t P);
 bool x1_planes(const msfno_block_desc* d, const msfno_sht_plan_s* g);
-bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b);
-// the inner-skip GEMM on the x3h engine (gemm_x3), forked after the norm0 statistics
+// the inner-skip GEMM on the x3h engine: the carve functions reserve b.xs for it
 bool skip_x3(const msfno_block_desc* d);
 // plan construction (mask: optional m-set, see SpecLayout::build)
 int plan_create(int nlat, int nlon, int lmax, int mmax, int inverse,

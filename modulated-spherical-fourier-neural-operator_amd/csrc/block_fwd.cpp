@@ -1,8 +1,9 @@
-// Forward orchestration of the fused SFNO block: workspace layout, the side stream of
-// the inner skip, the spectral filter, the channel MLP and the msfno_block_* entry points.
+// Forward orchestration of the fused SFNO block: workspace layout, the side stream, the
+// spectral filter (run_filter: one chain per engine), the inner skip (skip_gemm, skip_fork,
+// skip_fork_point: shared with band.cpp), run_spectral, the channel MLP and the
+// msfno_block_* entry points.
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <map>
 #include <mutex>
 
@@ -299,181 +300,196 @@ int check_pair(const msfno_block_desc* d, const msfno_sht_plan_s* f,
   return MSFNO_OK;
 }
 
-int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
-                      const BlockBufs& b, int B, hipStream_t s) {
-  const int64_t C = d->C;
-  const SpecLayout& L = f->spec;
-  if (d->filter_type == MSFNO_FILTER_NONLINEAR) {
-    const int nl = d->spectral_layers;
-    const int64_t Hs = d->spec_hidden;
-    prof(ST_SPEC_PREP, s);
-    const bool x6 = spec_use_x6() && b.dw.spec[0];
-    const bool c3m = !x6;  // fp32 engine: Gauss 3M complex GEMM (cgemm.hip)
-    if (x6 && spec_use_3m() && C <= Hs) {
-      // Gauss 3M complex GEMMs (gemm_x6c.hip): weights Wr, Wi, Wr+Wi of all layers in
-      // one launch; layer 0 splits its fp32 input while staging it
-      SpecWeightsX6p sw{};
-      sw.nlayers = nl + 1;
-      for (int l = 0; l <= nl; ++l) {
-        sw.w[l] = (l == nl) ? d->spec_wout : d->spec_w[l];
-        MSFNO_REQUIRE(sw.w[l], MSFNO_EINVAL, "missing spectral weight");
-        sw.ci[l] = (l == 0) ? (int)C : (int)Hs;
-        sw.co[l] = (l == nl) ? (int)C : (int)Hs;
-        sw.out[l] = static_cast<unsigned short*>(b.dw.spec[l]);
-      }
-      spec_weights_3m_layout(sw);
-      if (spec_use_x3h() && spec_x3h_range_ok(C, Hs, nl) && b.cs && L.ldT % 4 == 0) {
-        // x3h engine: two fp16 planes per value, three MFMAs per product; the layer
-        // scales (2 floats per layer) live behind layer 0's A image (inside wcache when
-        // the images are cached), the per-column input scales in b.cs
-        const int64_t a0 = round_up(6LL * round_up(sw.co[0], 128) * round_up(sw.ci[0], 16) * 2, 256);
-        MSFNO_REQUIRE((size_t)a0 + 2 * (nl + 1) * sizeof(float) <= b.dw.spec_b[0], MSFNO_EWORKSPACE,
-                      "x3h spectral scales do not fit behind layer 0's image");
-        sw.scl = reinterpret_cast<float*>(static_cast<char*>(b.dw.spec[0]) + a0);
-        if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_3m_x3h(sw, s));
-        const int ldcs = (int)round_up(L.Tp, 4);
-        MSFNO_TRY(launch_spec_colscale(b.Sa, B, (int)C, (int)L.Tp, (int)L.ldT, b.cs, ldcs, s));
-        unsigned short* cur = nullptr;
-        for (int l = 0; l <= nl; ++l) {
-          prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
-          unsigned short* out = l == nl ? nullptr
-                                        : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
-          MSFNO_TRY(gemm_x3c(sw.out[l], sw.co[l], sw.ci[l], l == 0 ? b.Sa : nullptr, (int)L.ldT,
-                             l == 0 ? nullptr : cur, (int)L.Tp, out, l == nl ? b.Sa : nullptr,
-                             (int)L.ldT, l < nl, sw.scl + 2 * l + 1,
-                             l == 0 ? b.cs : (l == nl ? b.cs + (int64_t)B * ldcs : nullptr), ldcs, B,
-                             s));
-          cur = out;
-        }
-        return MSFNO_OK;
-      }
-      if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_3m(sw, s));
-      const int ldTx = (int)round_up(L.Tp, 8);
-      unsigned short* cur = nullptr;
-      // layer 0 stages S fp32 and splits it in-kernel; hidden activations travel in the
-      // tiled layout (gemm_x6c.hip)
-      for (int l = 0; l <= nl; ++l) {
-        prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
-        unsigned short* out = l == nl ? nullptr
-                                      : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
-        if (l == 0)
-          MSFNO_TRY(gemm_x6c_f32b(sw.out[0], sw.co[0], sw.ci[0], b.Sa, (int)L.ldT, (int)L.Tp, out,
-                                  ldTx, true, B, s));
-        else
-          MSFNO_TRY(gemm_x6c(sw.out[l], sw.co[l], sw.ci[l], cur, (int)L.Tp, ldTx, out,
-                             l == nl ? b.Sa : nullptr, (int)L.ldT, l < nl, B, s));
-        cur = out;
-      }
-      return MSFNO_OK;
-    }
-    const bool split_l0 = x6 && C <= Hs;  // layer 0 input split into Sc (below)
-    if (x6) {
-      // every layer's real-ified weight straight into its x6p A image, one launch
-      SpecWeightsX6p sw{};
-      sw.nlayers = nl + 1;
-      for (int l = 0; l <= nl; ++l) {
-        sw.w[l] = (l == nl) ? d->spec_wout : d->spec_w[l];
-        MSFNO_REQUIRE(sw.w[l], MSFNO_EINVAL, "missing spectral weight");
-        sw.ci[l] = (l == 0) ? (int)C : (int)Hs;
-        sw.co[l] = (l == nl) ? (int)C : (int)Hs;
-        sw.out[l] = static_cast<unsigned short*>(b.dw.spec[l]);
-      }
-      spec_weights_x6p_layout(sw);
-      if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_x6p(sw, s));
-    }
-    for (int l = 0; l <= nl; ++l) {
-      const int ci = (l == 0) ? (int)C : (int)Hs;
-      const int co = (l == nl) ? (int)C : (int)Hs;
-      const float* w = (l == nl) ? d->spec_wout : d->spec_w[l];
-      MSFNO_REQUIRE(w, MSFNO_EINVAL, "missing spectral weight");
-      if (x6 && (l > 0 || split_l0)) continue;  // prepared above
-      if (c3m)
-        MSFNO_TRY(launch_split_complex_weight(w, b.Wexp[l], b.Wexp[l] + (int64_t)ci * co, ci, co, s));
-      else
-        MSFNO_TRY(launch_expand_complex_weight(w, b.Wexp[l], ci, co, s));
-    }
-    const float* in = b.Sa;
-    for (int l = 0; l <= nl; ++l) {
-      const int ci = (l == 0) ? (int)C : (int)Hs;
-      const int co = (l == nl) ? (int)C : (int)Hs;
-      float* out = (l == nl) ? b.Sa : ((l & 1) ? b.Sc : b.Sb);
-      prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
-      if (x6) {
-        // real-ified [[Wr, -Wi], [Wi, Wr]] GEMM on the x6 engine, ComplexReLU(real)
-        // = ReLU on the real rows of each batch block, in the epilogue.  Hidden
-        // activations travel as bf16x3 planes [b][plane][2 Hs][ldTx]: layer 0
-        // splits its fp32 input in-kernel, later layers stage planes by LDS-DMA
-        // (gemm_x6p), the output layer writes fp32 S for the inverse Legendre.
-        const int64_t ldTx = round_up(L.Tp, 8);
-        GemmEpi e;
-        if (l < nl) {
-          e.relu_period = 2 * co;
-          e.relu_rows = co;
-          e.c_planes = reinterpret_cast<unsigned short*>(out);
-          e.c_plane_stride = 2LL * co * ldTx;
-        }
-        const int ldc = l < nl ? (int)ldTx : (int)L.ldT;
-        const int64_t sC = l < nl ? 3 * 2LL * co * ldTx : 2LL * co * L.ldT;
-        if (l > 0 || split_l0) e.a_planes = static_cast<const unsigned short*>(b.dw.spec[l]);
-        if (l == 0 && split_l0) {  // Sc is free during layer 0
-          // layer 0's fp32 input (the forward Legendre output) -> planes in Sc: one
-          // streaming pass, then the LDS-DMA kernel (cheaper than splitting the
-          // 2C x T operand once per M-tile inside the GEMM)
-          unsigned short* inx = reinterpret_cast<unsigned short*>(b.Sc);
-          MSFNO_TRY(launch_split_planes(in, inx, 2 * ci, (int)L.Tp, (int)L.ldT, 2LL * ci * L.ldT,
-                                        (int)ldTx, 2LL * ci * ldTx, 3 * 2LL * ci * ldTx, B, s));
-          e.b_planes = inx;
-          e.b_plane_stride = 2LL * ci * ldTx;
-          MSFNO_TRY(gemm_x6p(b.Wexp[l], out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci, (int)ldTx, ldc, 0,
-                             3 * 2LL * ci * ldTx, sC, B, e, b.dw.spec[l], b.dw.spec_b[l], s));
-        } else if (l == 0) {
-          MSFNO_TRY(gemm_dense(TILE_128x128, b.Wexp[l], in, out, 2 * co, (int)L.Tp,
-                               2 * ci, 2 * ci, (int)L.ldT, ldc, 0, 2LL * ci * L.ldT, sC, B, e,
-                               b.dw.spec[l], b.dw.spec_b[l], s));
-        } else {
-          e.b_planes = reinterpret_cast<const unsigned short*>(in);
-          e.b_plane_stride = 2LL * ci * ldTx;
-          MSFNO_TRY(gemm_x6p(b.Wexp[l], out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci, (int)ldTx, ldc, 0,
-                             3 * 2LL * ci * ldTx, sC, B, e, b.dw.spec[l], b.dw.spec_b[l], s));
-        }
-      } else {
-        // Gauss 3-multiplication complex GEMM (cgemm.hip), ComplexReLU(real) fused
-        MSFNO_TRY(gemm_c3m(b.Wexp[l], b.Wexp[l] + (int64_t)ci * co, in, out, co, ci, (int)L.Tp,
-                           (int)L.ldT, (int)L.ldT, 2LL * ci * L.ldT, 2LL * co * L.ldT, B, l < nl,
-                           s));
-      }
-      in = out;
-    }
-  } else {
-    MSFNO_REQUIRE(d->lin_w, MSFNO_EINVAL, "missing linear spectral weight");
-    prof(ST_LIN_GATHER, s);
-    MSFNO_TRY(launch_spec_to_tril(*f, b.Sa, b.xt, B, (int)C, s));
-    prof(ST_LIN_CONTRACT, s);
-    MSFNO_TRY(launch_compl_contract(b.xt, d->lin_w, b.yt, B, (int)C, (int)C, L.T, s));
-    prof(ST_LIN_SCATTER, s);
-    MSFNO_TRY(launch_tril_to_spec(*f, b.yt, b.Sa, B, (int)C, s));
+// the spectral MLP's layers 0 .. spectral_layers (the last is the output layer): each one's
+// (ci, co, weight) and A image (b.dw.spec), for every chain and the one-launch weight
+// preparations
+static int spec_layers(const msfno_block_desc* d, const BlockBufs& b, SpecWeightsX6p& sw) {
+  const int nl = d->spectral_layers;
+  sw = SpecWeightsX6p{};
+  sw.nlayers = nl + 1;
+  for (int l = 0; l <= nl; ++l) {
+    sw.w[l] = (l == nl) ? d->spec_wout : d->spec_w[l];
+    MSFNO_REQUIRE(sw.w[l], MSFNO_EINVAL, "missing spectral weight");
+    sw.ci[l] = (int)(l == 0 ? d->C : d->spec_hidden);
+    sw.co[l] = (int)(l == nl ? d->C : d->spec_hidden);
+    sw.out[l] = static_cast<unsigned short*>(b.dw.spec[l]);
   }
-  (void)g;
   return MSFNO_OK;
+}
+
+// x3h engine (gemm_x3c): two fp16 planes per value, three MFMAs per product; the layer
+// scales (2 floats per layer) live behind layer 0's A image (inside wcache when
+// the images are cached), the per-column input scales in b.cs
+static int filter_x3h(const msfno_block_desc* d, const SpecLayout& L, const BlockBufs& b,
+                      SpecWeightsX6p& sw, int B, hipStream_t s) {
+  const int nl = d->spectral_layers;
+  const int64_t a0 = round_up(6LL * round_up(sw.co[0], 128) * round_up(sw.ci[0], 16) * 2, 256);
+  MSFNO_REQUIRE((size_t)a0 + 2 * (nl + 1) * sizeof(float) <= b.dw.spec_b[0], MSFNO_EWORKSPACE,
+                "x3h spectral scales do not fit behind layer 0's image");
+  sw.scl = reinterpret_cast<float*>(static_cast<char*>(b.dw.spec[0]) + a0);
+  if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_3m_x3h(sw, s));
+  const int ldcs = (int)round_up(L.Tp, 4);
+  MSFNO_TRY(launch_spec_colscale(b.Sa, B, (int)d->C, (int)L.Tp, (int)L.ldT, b.cs, ldcs, s));
+  unsigned short* cur = nullptr;
+  for (int l = 0; l <= nl; ++l) {
+    prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
+    unsigned short* out = l == nl ? nullptr
+                                  : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
+    MSFNO_TRY(gemm_x3c(sw.out[l], sw.co[l], sw.ci[l], l == 0 ? b.Sa : nullptr, (int)L.ldT,
+                       l == 0 ? nullptr : cur, (int)L.Tp, out, l == nl ? b.Sa : nullptr,
+                       (int)L.ldT, l < nl, sw.scl + 2 * l + 1,
+                       l == 0 ? b.cs : (l == nl ? b.cs + (int64_t)B * ldcs : nullptr), ldcs, B,
+                       s));
+    cur = out;
+  }
+  return MSFNO_OK;
+}
+
+// x6 engine, Gauss 3M complex GEMMs (gemm_x6c.hip): layer 0 stages S fp32 and splits it
+// in-kernel; hidden activations travel in the tiled layout
+static int filter_x6_3m(const msfno_block_desc* d, const SpecLayout& L, const BlockBufs& b,
+                        const SpecWeightsX6p& sw, int B, hipStream_t s) {
+  const int nl = d->spectral_layers;
+  if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_3m(sw, s));
+  const int ldTx = (int)round_up(L.Tp, 8);
+  unsigned short* cur = nullptr;
+  for (int l = 0; l <= nl; ++l) {
+    prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
+    unsigned short* out = l == nl ? nullptr
+                                  : reinterpret_cast<unsigned short*>((l & 1) ? b.Sc : b.Sb);
+    if (l == 0)
+      MSFNO_TRY(gemm_x6c_f32b(sw.out[0], sw.co[0], sw.ci[0], b.Sa, (int)L.ldT, (int)L.Tp, out,
+                              ldTx, true, B, s));
+    else
+      MSFNO_TRY(gemm_x6c(sw.out[l], sw.co[l], sw.ci[l], cur, (int)L.Tp, ldTx, out,
+                         l == nl ? b.Sa : nullptr, (int)L.ldT, l < nl, B, s));
+    cur = out;
+  }
+  return MSFNO_OK;
+}
+
+// x6 engine, real-ified [[Wr, -Wi], [Wi, Wr]] GEMMs (MSFNO_SPEC_3M=0, or C > Hs),
+// ComplexReLU(real) = ReLU on the real rows of each batch block, in the epilogue.  Hidden
+// activations travel as bf16x3 planes [b][plane][2 Hs][ldTx]: later layers stage planes by
+// LDS-DMA (gemm_x6p), the output layer writes fp32 S for the inverse Legendre.
+static int filter_x6p(const msfno_block_desc* d, const SpecLayout& L, const BlockBufs& b,
+                      SpecWeightsX6p& sw, int B, hipStream_t s) {
+  const int nl = d->spectral_layers;
+  const bool split_l0 = d->C <= d->spec_hidden;  // layer 0 input split into Sc (below)
+  // every layer's real-ified weight straight into its x6p A image, one launch
+  spec_weights_x6p_layout(sw);
+  if (!wcache_ready(d)) MSFNO_TRY(launch_spec_weights_x6p(sw, s));
+  if (!split_l0) MSFNO_TRY(launch_expand_complex_weight(sw.w[0], b.Wexp[0], sw.ci[0], sw.co[0], s));
+  const int64_t ldTx = round_up(L.Tp, 8);
+  const float* in = b.Sa;
+  for (int l = 0; l <= nl; ++l) {
+    const int ci = sw.ci[l], co = sw.co[l];
+    float* out = (l == nl) ? b.Sa : ((l & 1) ? b.Sc : b.Sb);
+    prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
+    GemmEpi e;
+    if (l < nl) {
+      e.relu_period = 2 * co;
+      e.relu_rows = co;
+      e.c_planes = reinterpret_cast<unsigned short*>(out);
+      e.c_plane_stride = 2LL * co * ldTx;
+    }
+    const int ldc = l < nl ? (int)ldTx : (int)L.ldT;
+    const int64_t sC = l < nl ? 3 * 2LL * co * ldTx : 2LL * co * L.ldT;
+    if (l == 0 && !split_l0) {  // layer 0 splits its fp32 input in-kernel
+      MSFNO_TRY(gemm_dense(TILE_128x128, b.Wexp[l], in, out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci,
+                           (int)L.ldT, ldc, 0, 2LL * ci * L.ldT, sC, B, e, b.dw.spec[l],
+                           b.dw.spec_b[l], s));
+    } else {
+      e.a_planes = static_cast<const unsigned short*>(b.dw.spec[l]);
+      e.b_planes = reinterpret_cast<const unsigned short*>(in);
+      if (l == 0) {  // Sc is free during layer 0
+        // layer 0's fp32 input (the forward Legendre output) -> planes in Sc: one
+        // streaming pass, then the LDS-DMA kernel (cheaper than splitting the
+        // 2C x T operand once per M-tile inside the GEMM)
+        unsigned short* inx = reinterpret_cast<unsigned short*>(b.Sc);
+        MSFNO_TRY(launch_split_planes(in, inx, 2 * ci, (int)L.Tp, (int)L.ldT, 2LL * ci * L.ldT,
+                                      (int)ldTx, 2LL * ci * ldTx, 3 * 2LL * ci * ldTx, B, s));
+        e.b_planes = inx;
+      }
+      e.b_plane_stride = 2LL * ci * ldTx;
+      MSFNO_TRY(gemm_x6p(b.Wexp[l], out, 2 * co, (int)L.Tp, 2 * ci, 2 * ci, (int)ldTx, ldc, 0,
+                         3 * 2LL * ci * ldTx, sC, B, e, b.dw.spec[l], b.dw.spec_b[l], s));
+    }
+    in = out;
+  }
+  return MSFNO_OK;
+}
+
+// fp32 engine: Gauss 3-multiplication complex GEMMs (cgemm.hip), ComplexReLU(real) fused
+static int filter_f32(const msfno_block_desc* d, const SpecLayout& L, const BlockBufs& b,
+                      const SpecWeightsX6p& sw, int B, hipStream_t s) {
+  const int nl = d->spectral_layers;
+  for (int l = 0; l <= nl; ++l) {
+    const int ci = sw.ci[l], co = sw.co[l];
+    MSFNO_TRY(launch_split_complex_weight(sw.w[l], b.Wexp[l], b.Wexp[l] + (int64_t)ci * co, ci, co, s));
+  }
+  const float* in = b.Sa;
+  for (int l = 0; l <= nl; ++l) {
+    const int ci = sw.ci[l], co = sw.co[l];
+    float* out = (l == nl) ? b.Sa : ((l & 1) ? b.Sc : b.Sb);
+    prof(l == nl ? ST_SPEC_OUT : ST_SPEC_L0 + std::min(l, 3), s);
+    MSFNO_TRY(gemm_c3m(b.Wexp[l], b.Wexp[l] + (int64_t)ci * co, in, out, co, ci, (int)L.Tp,
+                       (int)L.ldT, (int)L.ldT, 2LL * ci * L.ldT, 2LL * co * L.ldT, B, l < nl, s));
+    in = out;
+  }
+  return MSFNO_OK;
+}
+
+// linear filter: gather S to tril order, per-mode contraction, scatter back
+static int filter_linear(const msfno_block_desc* d, const msfno_sht_plan_s& f, const BlockBufs& b,
+                         int B, hipStream_t s) {
+  const int C = (int)d->C;
+  MSFNO_REQUIRE(d->lin_w, MSFNO_EINVAL, "missing linear spectral weight");
+  prof(ST_LIN_GATHER, s);
+  MSFNO_TRY(launch_spec_to_tril(f, b.Sa, b.xt, B, C, s));
+  prof(ST_LIN_CONTRACT, s);
+  MSFNO_TRY(launch_compl_contract(b.xt, d->lin_w, b.yt, B, C, C, f.spec.T, s));
+  prof(ST_LIN_SCATTER, s);
+  MSFNO_TRY(launch_tril_to_spec(f, b.yt, b.Sa, B, C, s));
+  return MSFNO_OK;
+}
+
+int run_filter(const msfno_block_desc* d, msfno_sht_plan_s* f, const BlockBufs& b, int B,
+               hipStream_t s) {
+  if (d->filter_type != MSFNO_FILTER_NONLINEAR) return filter_linear(d, *f, b, B, s);
+  const int64_t C = d->C, Hs = d->spec_hidden;
+  const SpecLayout& L = f->spec;
+  prof(ST_SPEC_PREP, s);
+  const bool x6 = spec_use_x6() && b.dw.spec[0];
+  SpecWeightsX6p sw;
+  MSFNO_TRY(spec_layers(d, b, sw));
+  if (!x6) return filter_f32(d, L, b, sw, B, s);
+  if (!(spec_use_3m() && C <= Hs)) return filter_x6p(d, L, b, sw, B, s);
+  // 3M: weights Wr, Wi, Wr+Wi of all layers in one launch
+  spec_weights_3m_layout(sw);
+  if (spec_use_x3h() && spec_x3h_range_ok(C, Hs, d->spectral_layers) && b.cs && L.ldT % 4 == 0)
+    return filter_x3h(d, L, b, sw, B, s);
+  return filter_x6_3m(d, L, b, sw, B, s);
 }
 
 int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_s* g,
                  const BlockBufs& b, const float* x, int B, bool norm0, hipStream_t s,
-                 const C2RPlanes* xplanes, const std::function<int()>& after_fft,
-                 const std::function<int()>& after_norm0, const std::function<int()>& after_leg,
-                 const std::function<int()>& before_inv) {
+                 const InnerSkip* skip) {
   const int64_t C = d->C, BC = (int64_t)B * C, R = 2 * BC;
+  const SkipFork at = skip ? skip->at : SKIP_NONE;
+  if (at == SKIP_FIRST) MSFNO_TRY(skip_fork(*skip, s));
   prof(ST_FFT_FWD, s);
   const float scale = (float)(2.0 * M_PI / f->nlon);
+  const C2RPlanes xp{b.x1p, (int)C, f->nlat};
   MSFNO_TRY(launch_fft_r2c_rows(f->fft, x, b.Xn, norm0 ? b.rs0 : nullptr, BC * f->nlat, f->mmax,
-                                scale, s, xplanes));
-  if (after_fft) MSFNO_TRY(after_fft());
+                                scale, s, at == SKIP_AFTER_FFT ? &xp : nullptr));
+  if (at == SKIP_AFTER_FFT) MSFNO_TRY(skip_fork(*skip, s));
   if (norm0) {
     prof(ST_NORM0, s);
     MSFNO_TRY(launch_chan_affine(b.rs0, f->nlat, f->nlon, f->nlon, B, (int)C, d->norm0_w,
                                  d->norm0_b, d->norm_eps, nullptr, nullptr, 0.f, b.sc0, b.sh0,
                                  s, b.xs, b.lsig));
-    if (after_norm0) MSFNO_TRY(after_norm0());
+    if (at == SKIP_AFTER_NORM0) MSFNO_TRY(skip_fork(*skip, s));
   }
   prof(ST_TRANSPOSE_FWD, s);
   if (norm0 && b.lsig && b.isr && x3f_usable(f)) {
@@ -489,9 +505,8 @@ int run_spectral(const msfno_block_desc* d, msfno_sht_plan_s* f, msfno_sht_plan_
     prof(ST_LEG_FWD, s);
     MSFNO_TRY(legendre_fwd(f, b.Xt, b.Sa, (int)R, s));
   }
-  if (after_leg) MSFNO_TRY(after_leg());
-  MSFNO_TRY(run_filter(d, f, g, b, B, s));
-  if (before_inv) MSFNO_TRY(before_inv());
+  MSFNO_TRY(run_filter(d, f, b, B, s));
+  if (at == SKIP_BEFORE_INV) MSFNO_TRY(skip_fork(*skip, s));
   prof(ST_LEG_INV, s);
   // (the linear filter on S writes its output to Sb)
   MSFNO_TRY(legendre_inv(g, b.Sa, b.Yt, (int)R, s));
@@ -557,6 +572,11 @@ int run_mlp(const msfno_block_desc* d, const float* W1f, const float* b1f, const
                     dw.fc2_b, s);
 }
 
+// ---------------------------------------------------------------------------
+// the inner skip: engine dispatch, fork / join, fork point (block_forward_impl and
+// msfno_band_block_stage; DESIGN.md §5 has the table)
+// ---------------------------------------------------------------------------
+
 // the inner-skip GEMM reads fp32 x and splits it in-kernel (gemm_x6), forked before
 // the forward FFT; MSFNO_SKIP_PLANES=1: x as bf16x3 planes written by the forward FFT
 // (into the x1 plane buffer), the GEMM forked after it.  With the fused MLP the fp32
@@ -573,9 +593,72 @@ bool skip_x3(const msfno_block_desc* d) {
   return on && gemm_use_x6() && !skip_planes_env() && d->inner_skip == MSFNO_SKIP_LINEAR;
 }
 
-bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b) {
+static bool skip_planes(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b) {
   return skip_planes_env() && b.x1p && b.dw.skip && d->inner_skip == MSFNO_SKIP_LINEAR &&
          fft_r2c_planes_supported(f->fft, f->mmax);
+}
+
+// x3h (b.xs: its per-channel scales come from the norm0 statistics): forked after them.  The
+// skip slows whatever it overlaps by about its own length: forked after the forward
+// Legendre instead (overlapping only the MFMA-bound spectral layers) measured equal
+// (160.8 / 159.9 vs 160.7 / 159.9 fields/s, round 5).  The linear filter forks it after
+// the per-mode contraction, so its 2.1 GB do not share HBM with the 34 GB weight stream:
+// 94.0 / 94.2 vs 92.2 / 92.3 fields/s (profiles/r05_b).
+// x6 planes: the forward FFT also writes x as bf16x3 planes into the x1 plane buffer (dead
+// until the inverse FFT, which runs after the skip GEMM); the GEMM is forked after the FFT
+// and stages B by LDS-DMA (gemm_x6p) instead of splitting fp32 x in-kernel.  A separate
+// skip input is not what the FFT reads: fp32, forked first.
+// Otherwise (x6 or fp32 engine on fp32 x: depends only on the input) forked first.
+SkipFork skip_fork_point(const msfno_block_desc* d, const msfno_sht_plan_s* f, const BlockBufs& b,
+                         bool separate_input) {
+  if (d->inner_skip != MSFNO_SKIP_LINEAR) return SKIP_NONE;
+  if (b.xs) return d->filter_type == MSFNO_FILTER_NONLINEAR ? SKIP_AFTER_NORM0 : SKIP_BEFORE_INV;
+  return skip_planes(d, f, b) && !separate_input ? SKIP_AFTER_FFT : SKIP_FIRST;
+}
+
+// the skip GEMM on stream ss: x3h on the scales b.xs (skip_h at C = 256, else gemm_x3), x6
+// on the x planes the forward FFT wrote (gemm_x6p), else gemm_dense on fp32 sx
+static int skip_gemm(const InnerSkip& k, hipStream_t ss) {
+  const msfno_block_desc* d = k.d;
+  const BlockBufs& b = *k.b;
+  const int64_t C = d->C, P = k.P;
+  const int B = k.B;
+  prof(ST_SKIP, ss);
+  GemmEpi e;
+  e.bias = d->skip_b;
+  if (k.own_scales) MSFNO_TRY(launch_chan_pow2_scale(k.sx, (int64_t)B * C, P, b.xs, ss));
+  if (b.xs && C == 256 && skip_h_env()) {
+    MSFNO_TRY(launch_skip_h(d->skip_w, b.xs, k.sx, k.x1, d->skip_b, B, P, b.dw.skip, b.dw.skip_b,
+                            ss, k.quarter_cu));
+  } else if (b.xs) {
+    MSFNO_TRY(gemm_x3(d->skip_w, (int)C, b.xs, k.sx, k.x1, (int)C, (int)P, (int)C, (int)P, (int)P,
+                      C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
+  } else if (k.at == SKIP_AFTER_FFT) {
+    e.b_planes = b.x1p;
+    e.b_plane_stride = C * P;
+    MSFNO_TRY(gemm_x6p(d->skip_w, k.x1, (int)C, (int)P, (int)C, (int)C, (int)P, (int)P, 0,
+                       3 * C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
+  } else {
+    // sx: global_conv's skip input is the residual, not the filter input x
+    MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, k.sx, k.x1, (int)C, (int)P, (int)C, (int)C,
+                         (int)P, (int)P, 0, C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
+  }
+  return MSFNO_OK;
+}
+
+int skip_fork(const InnerSkip& k, hipStream_t s) {
+  hipStream_t ss = s;
+  if (k.side) {  // fork
+    MSFNO_CHECK_HIP(hipEventRecord(k.side->fork, s));
+    MSFNO_CHECK_HIP(hipStreamWaitEvent(k.side->side, k.side->fork, 0));
+    ss = k.side->side;
+  }
+  MSFNO_TRY(skip_gemm(k, ss));
+  if (k.side) {
+    prof(ST_END, ss);
+    MSFNO_CHECK_HIP(hipEventRecord(k.join, ss));
+  }
+  return MSFNO_OK;
 }
 
 // x1 (the MLP input) written by the inverse FFT as bf16x3 planes: x6 engine, an
@@ -699,75 +782,26 @@ static int block_forward_impl(const msfno_block_desc* d, msfno_sht_plan_t f, msf
   const int act = d->filter_type == MSFNO_FILTER_LINEAR ? 1 : 0;  // GELU after skip (linear only)
 
   // ---- inner skip 1x1 conv (depends only on x): x1 = Ws·x + bs, on the side stream ----
-  // With x6 planes the forward FFT also writes x as bf16x3 planes into the x1 plane
-  // buffer (dead until the inverse FFT, which runs after the skip GEMM): the skip
-  // GEMM is forked after the forward FFT and stages B by LDS-DMA (gemm_x6p) instead
-  // of splitting fp32 x in-kernel.
+  // run_spectral forks it at skip.at (skip_fork_point)
   float* x1 = x1_ext ? x1_ext : b.x1;
   const float* sx = skip_x ? skip_x : x;
   std::shared_ptr<SideCtx> side;
-  const bool xpl = skip_planes(d, f, b) && sx == x;  // the FFT writes planes of x
-  const C2RPlanes xp{b.x1p, (int)C, f->nlat};
-  auto launch_skip = [&]() -> int {
-    hipStream_t ss = s;
-    if (side) {  // fork
-      MSFNO_CHECK_HIP(hipEventRecord(side->fork, s));
-      MSFNO_CHECK_HIP(hipStreamWaitEvent(side->side, side->fork, 0));
-      ss = side->side;
-    }
-    prof(ST_SKIP, ss);
-    GemmEpi e;
-    e.bias = d->skip_b;
-    // a separate skip input has no norm0 statistics: its x3h B-row scales from its max
-    if (b.xs && sx != x) MSFNO_TRY(launch_chan_pow2_scale(sx, (int64_t)B * C, P, b.xs, ss));
-    if (b.xs && C == 256 && skip_h_env()) {
-      // the quarter-CU side grid only where the skip is forked at the block start and
-      // overlaps the whole SHT + spectral chain (non-linear filter); the other filters fork
-      // it after the contraction (skip_late below), where it is on the critical path (1.80 vs 0.79 ms,
-      // linear 85.9 vs 97.5 fields/s, profiles/r06_j)
-      MSFNO_TRY(launch_skip_h(d->skip_w, b.xs, sx, x1, d->skip_b, B, P, b.dw.skip, b.dw.skip_b,
-                              ss, side != nullptr && d->filter_type == MSFNO_FILTER_NONLINEAR));
-    } else if (b.xs) {
-      MSFNO_TRY(gemm_x3(d->skip_w, (int)C, b.xs, sx, x1, (int)C, (int)P, (int)C, (int)P, (int)P,
-                        C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
-    } else if (xpl) {
-      e.b_planes = b.x1p;
-      e.b_plane_stride = C * P;
-      MSFNO_TRY(gemm_x6p(d->skip_w, x1, (int)C, (int)P, (int)C, (int)C, (int)P, (int)P, 0,
-                         3 * C * P, C * P, B, e, b.dw.skip, b.dw.skip_b, ss));
-    } else {
-      // sx: global_conv's skip input is the residual, not the filter input x
-      MSFNO_TRY(gemm_dense(TILE_128x256, d->skip_w, sx, x1, (int)C, (int)P, (int)C,
-                           (int)C, (int)P, (int)P, 0, C * P, C * P, B, e, b.dw.skip, b.dw.skip_b,
-                           ss));
-    }
-    if (side) {
-      prof(ST_END, ss);
-      MSFNO_CHECK_HIP(hipEventRecord(side->join, ss));
-    }
-    return MSFNO_OK;
-  };
-  if (d->inner_skip == MSFNO_SKIP_LINEAR) {
+  InnerSkip skip{d, &b, sx, x1, B, P, skip_fork_point(d, f, b, sx != x)};
+  if (skip.at != SKIP_NONE) {
     MSFNO_REQUIRE(d->skip_w, MSFNO_EINVAL, "missing inner_skip weight");
     MSFNO_TRY(side_ctx(&side, s));
-    if (!xpl && !b.xs) MSFNO_TRY(launch_skip());
+    skip.side = side.get();
+    skip.join = side ? side->join : nullptr;
+    // a separate skip input has no norm0 statistics: its x3h B-row scales from its max
+    // (the block only: the band's skip input is always the filter's)
+    skip.own_scales = b.xs && sx != x;
+    // the quarter-CU side grid only where the skip is forked at the block start and
+    // overlaps the whole SHT + spectral chain (non-linear filter); the other filters fork
+    // it after the contraction (SKIP_BEFORE_INV), where it is on the critical path (1.80 vs
+    // 0.79 ms, linear 85.9 vs 97.5 fields/s, profiles/r06_j)
+    skip.quarter_cu = side && d->filter_type == MSFNO_FILTER_NONLINEAR;
   }
-  // The skip is forked after the norm0 statistics (x3h: its per-channel scales come from
-  // them).  It slows whatever it overlaps by about its own length: forked after the forward
-  // Legendre instead (overlapping only the MFMA-bound spectral layers) measured equal
-  // (160.8 / 159.9 vs 160.7 / 159.9 fields/s, round 5).  The linear filter forks it after
-  // the per-mode contraction, so its 2.1 GB do not share HBM with the 34 GB weight stream:
-  // 94.0 / 94.2 vs 92.2 / 92.3 fields/s (profiles/r05_b)
-  const bool skip_late = d->filter_type != MSFNO_FILTER_NONLINEAR;
-  if (b.xs && skip_late)
-    MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s, nullptr, std::function<int()>(),
-                           std::function<int()>(), std::function<int()>(), launch_skip));
-  else if (b.xs)
-    MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s, nullptr, std::function<int()>(), launch_skip));
-  else if (xpl)
-    MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s, &xp, launch_skip));
-  else
-    MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s));
+  MSFNO_TRY(run_spectral(d, f, g, b, x, B, true, s, &skip));
   if (side) MSFNO_CHECK_HIP(hipStreamWaitEvent(s, side->join, 0));  // join
   // ---- filter output + skip (+ GELU for the linear filter) -> x1, norm1 partials ---
   const float* skip_src = d->inner_skip == MSFNO_SKIP_LINEAR ? x1

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from block_util import make_block
-from golden_util import golden_files, load
+from golden_util import golden_files, load, wiring_cfg
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -47,6 +47,45 @@ def test_sharded_block_matches_golden(path, world):
     assert y.shape == want.shape
     assert (y - want).abs().max().item() < 1e-4
     assert (y - y1).abs().max().item() < 2e-5
+
+
+SKIP_ENGINE_CASES = ["c1b2_nl_film_middle.npz", "lg_lin_film_middle.npz"]
+
+
+def _skip_engine_child():
+    """Both bars of test_sharded_block_matches_golden, world 2, on the two smallest fixtures
+    with a linear inner skip on either filter (a filmed batch of two; a Gauss grid)."""
+    for name in SKIP_ENGINE_CASES:
+        meta, params, arrays, _ = load([p for p in golden_files() if os.path.basename(p) == name][0])
+        assert wiring_cfg(meta)[0] == "linear"
+        blk, _, _ = make_block(meta, params)
+        blk = blk.to(DEV)
+        x, g, b = (arrays[k].to(DEV) for k in ("x", "gamma", "beta"))
+        with torch.no_grad():
+            y = _sharded(blk, x, g, b, meta["scale"], 2).cpu()
+            y1 = blk(x, g, b, meta["scale"]).cpu()
+        e_gold, e_self = (y - arrays["y"]).abs().max().item(), (y - y1).abs().max().item()
+        print(f"{name}: vs golden {e_gold:.3e}, vs unsharded {e_self:.3e}")
+        assert e_gold < 1e-4
+        assert e_self < 2e-5
+
+
+@pytest.mark.parametrize("env", ["MSFNO_SKIP_X3H=0", "MSFNO_ENGINE=x6", "MSFNO_SKIP_PLANES=1",
+                                 "MSFNO_GEMM=f32", "MSFNO_SIDE_STREAM=0"])
+def test_sharded_block_skip_engines(env):
+    """The band stages launch the inner skip through the block's dispatch (block_fwd.cpp:
+    skip_fork): every skip engine and fork point, and the serial schedule, under the sharded
+    block.  The engines are chosen once per process from the environment, so each runs in
+    a child process (this file as a script)."""
+    import subprocess
+    import sys
+    from conftest import PKG_DIR, REPO
+    k, v = env.split("=")
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "skip_engines"],
+                       env=dict(os.environ, PYTHONPATH=os.pathsep.join([REPO, PKG_DIR]), **{k: v}),
+                       cwd=os.path.dirname(__file__), capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    print(r.stdout.strip())
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -228,3 +267,9 @@ def test_sharded_block_two_processes_gloo(name, chunks):
         rows, part = res[r]
         y[:, :, rows] = torch.from_numpy(part)
     assert (y - arrays["y"]).abs().max().item() < 1e-4
+
+
+if __name__ == "__main__":
+    import sys
+    if sys.argv[1] == "skip_engines":
+        _skip_engine_child()
