@@ -640,6 +640,77 @@ int msfno_regrid(const float* x, int S_in, const int* slab, int S_out,
                  void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Statistics over time at fixed pixel: climatologies, score maps, the time mean and the
+ * variability of a long rollout (the reference forms its hour-of-year climatology on the
+ * host, data_process/climatology.py: IterMean, mean += (x - mean) / n; the Python mirror is
+ * msfno_amd/timestats.py).  A slab is a flat run of P = nlat * nlon fp32 elements: no
+ * latitude weights here.  A state is a uint32 count (S, P) and K fp32 planes (K, S, P),
+ * plane k at state + k * plane_stride (in floats, >= S * P); count, state and every input
+ * sit at any 4-byte alignment.  K is what the planes call returns for (kind, flags):
+ *
+ *   kind                  flags                K   planes
+ *   MSFNO_TSTATS_FIELD    0                    2   mean, m2
+ *   MSFNO_TSTATS_FIELD    MSFNO_TSTATS_MINMAX  4   mean, m2, lo, hi
+ *   MSFNO_TSTATS_ERROR    0                    3   mean_d, m2_d, mean_abs
+ *   MSFNO_TSTATS_ERROR    MSFNO_TSTATS_ANOM    8   mean_d, m2_d, mean_abs, mean_pa, m2_pa,
+ *                                                  mean_ta, m2_ta, c_pt
+ *
+ * FIELD takes x = in0 (in1 NULL) and the value a = x - c, or a = x without a climatology;
+ * ERROR takes p = in0, t = in1 with d = p - t and, with a climatology, pa = p - c and
+ * ta = t - c.  The anomaly planes are there iff the climatology is: an ERROR update has
+ * MSFNO_TSTATS_ANOM set iff clim is given.  A fresh state is count 0, planes 0, lo = +inf,
+ * hi = -inf.
+ *   Update folds a batch into one state.  in0, in1 are (B, S, P), batch element b at
+ *   in + b * batch_stride (in floats, any value: need not be a multiple of 4); clim is a
+ *   stack of (P) slabs and clim_slab a device int32[B * S], the slab of (b, s), every entry
+ *   >= 0 (the caller's contract; not range-checked), or both NULL.  Per pixel the B updates
+ *   are applied in the order b = 0 .. B - 1, in fp32 with a true division:
+ *     n += 1
+ *     delta = a - mean;  mean += delta / (float)n;  m2 = fma(delta, a - mean, m2)  (new mean)
+ *     mean_abs += (|d| - mean_abs) / n
+ *     c_pt = fma(pa - mean_pa_old, ta - mean_ta_new, c_pt)
+ *     lo = fminf(lo, a);  hi = fmaxf(hi, a)
+ *   so a call of B elements leaves the bits of B calls of one.  Every quantity is formed
+ *   from a difference, never from raw sums of squares.  With skip_nan != 0 an update
+ *   (b, s, i) is selected out, never multiplied by zero, where x or c is NaN (FIELD) or t or
+ *   c is NaN (ERROR; a NaN in p is never skipped, as in msfno_verify_region_sums): all of that
+ *   pixel's words keep their bits.  Without skip_nan a NaN poisons the moment planes of that
+ *   pixel and of no other (fminf and fmaxf pass it over: lo and hi stay numbers).
+ *   Traffic is B times the inputs plus one read and one write of the state.
+ *   Merge is dst <- dst (+) src over N = S * P elements, states of one kind and flags:
+ *     n = na + nb;  delta = mean_b - mean_a;  f = nb / n
+ *     mean = fma(delta, f, mean_a);  m2 = fma(delta^2, na f, m2_a + m2_b)
+ *     c_pt = fma(delta_pa delta_ta, na f, c_pt_a + c_pt_b);  mean_abs as mean;  lo by
+ *     fminf, hi by fmaxf
+ *   where nb == 0 dst keeps its bits and where na == 0 it takes src's.  It combines the
+ *   accumulators of processes or devices, and neighbouring climatology bins into a window.
+ *   dst and src must not overlap.
+ * No atomics and no workspace: results are bitwise reproducible and do not depend on the
+ * alignment of any buffer or on the launch geometry.  Nothing allocates, synchronises or
+ * memsets and the running count lives on the device, so both calls record into a graph and
+ * replay.  All three return MSFNO_EINVAL (msfno_last_error names the argument), before any
+ * launch, for a null required pointer, an extent below 1, an unknown kind or flag
+ * (MSFNO_TSTATS_MINMAX on ERROR, MSFNO_TSTATS_ANOM on FIELD), in1 missing for ERROR or given
+ * for FIELD, only one of clim / clim_slab, MSFNO_TSTATS_ANOM that disagrees with clim on an
+ * ERROR update, or a plane stride below S * P (N for the merge).  No K equals MSFNO_EINVAL.
+ * Added under ABI version 6: additions only, nothing existing changed.
+ * ------------------------------------------------------------------------- */
+#define MSFNO_TSTATS_FIELD 0
+#define MSFNO_TSTATS_ERROR 1
+#define MSFNO_TSTATS_MINMAX 1 /* flag of FIELD */
+#define MSFNO_TSTATS_ANOM 2   /* flag of ERROR */
+int msfno_tstats_planes(int kind, int flags);
+int msfno_tstats_update(int kind, int flags, const float* in0, const float* in1 /* or NULL */,
+                        long long batch_stride0, long long batch_stride1,
+                        const float* clim /* or NULL */, const int* clim_slab /* or NULL */,
+                        int B, int S, long long P, int skip_nan, uint32_t* count /* (S, P) */,
+                        float* state /* (K, S, P) */, long long plane_stride, void* stream);
+int msfno_tstats_merge(int kind, int flags, uint32_t* dst_count, float* dst_state,
+                       long long dst_plane_stride, const uint32_t* src_count,
+                       const float* src_state, long long src_plane_stride, long long N,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------
  * Graph-convolution FiLM generator (MSFNO/Models/gcn/gcn.py:96-167 GCN_custom,
  * layers.py:8-43 GraphConvolution; the Python mirror is msfno_amd/filmgen.py): the network
  * that turns the ocean points of an SST field into the FiLM vector, and its backward.  Per

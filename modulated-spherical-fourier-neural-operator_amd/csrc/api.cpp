@@ -1,5 +1,6 @@
 // libmsfno C-ABI: version, last error, and the thin validate-and-launch wrappers
-// (contractions, conv1x1, losses, verification, ensemble, export, regridding, spectrum).
+// (contractions, conv1x1, losses, verification, ensemble, export, regridding, statistics over
+// time, spectrum).
 #include <cmath>
 
 #include "block.h"
@@ -286,6 +287,57 @@ int msfno_regrid(const float* x, int S_in, const int* slab, int S_out,
   const RegridAxis lo = {lon->n_in, lon->n_out, lon->taps, lon->start, lon->count, lon->w};
   return launch_regrid(x, slab, S_out, la, lo, mask, skip_nan != 0, min_valid, fill, y,
                        (hipStream_t)stream);
+}
+
+int msfno_tstats_planes(int kind, int flags) {
+  const int K = tstats_planes(kind, flags);
+  MSFNO_REQUIRE(K > 0, MSFNO_EINVAL,
+                "tstats_planes: unknown kind, or a flag that the kind does not take");
+  return K;
+}
+
+int msfno_tstats_update(int kind, int flags, const float* in0, const float* in1,
+                        long long batch_stride0, long long batch_stride1, const float* clim,
+                        const int* clim_slab, int B, int S, long long P, int skip_nan,
+                        uint32_t* count, float* state, long long plane_stride, void* stream) {
+  MSFNO_REQUIRE(tstats_planes(kind, flags) > 0, MSFNO_EINVAL,
+                "tstats_update: unknown kind, or a flag that the kind does not take");
+  MSFNO_REQUIRE(in0, MSFNO_EINVAL, "tstats_update: in0 is null");
+  MSFNO_REQUIRE(count, MSFNO_EINVAL, "tstats_update: count is null");
+  MSFNO_REQUIRE(state, MSFNO_EINVAL, "tstats_update: state is null");
+  MSFNO_REQUIRE(B >= 1 && S >= 1 && P >= 1, MSFNO_EINVAL,
+                "tstats_update: B, S or P below 1");
+  MSFNO_REQUIRE((kind == MSFNO_TSTATS_ERROR) == (in1 != nullptr), MSFNO_EINVAL,
+                "tstats_update: in1 is required for ERROR and must be null for FIELD");
+  MSFNO_REQUIRE((clim == nullptr) == (clim_slab == nullptr), MSFNO_EINVAL,
+                "tstats_update: clim and clim_slab must both be set or both be null");
+  MSFNO_REQUIRE(kind != MSFNO_TSTATS_ERROR || ((flags & MSFNO_TSTATS_ANOM) != 0) == (clim != nullptr),
+                MSFNO_EINVAL,
+                "tstats_update: ERROR has the anomaly planes (flags) iff clim is given");
+  MSFNO_REQUIRE(plane_stride >= (long long)S * P, MSFNO_EINVAL,
+                "tstats_update: plane_stride is shorter than a plane");
+  return launch_tstats_update(kind, flags, in0, in1, batch_stride0, batch_stride1, clim,
+                              clim_slab, B, S, P, skip_nan, count, state, plane_stride,
+                              (hipStream_t)stream);
+}
+
+int msfno_tstats_merge(int kind, int flags, uint32_t* dst_count, float* dst_state,
+                       long long dst_plane_stride, const uint32_t* src_count,
+                       const float* src_state, long long src_plane_stride, long long N,
+                       void* stream) {
+  MSFNO_REQUIRE(tstats_planes(kind, flags) > 0, MSFNO_EINVAL,
+                "tstats_merge: unknown kind, or a flag that the kind does not take");
+  MSFNO_REQUIRE(dst_count && dst_state, MSFNO_EINVAL,
+                "tstats_merge: dst_count or dst_state is null");
+  MSFNO_REQUIRE(src_count && src_state, MSFNO_EINVAL,
+                "tstats_merge: src_count or src_state is null");
+  MSFNO_REQUIRE(N >= 1, MSFNO_EINVAL, "tstats_merge: N below 1");
+  MSFNO_REQUIRE(dst_plane_stride >= N, MSFNO_EINVAL,
+                "tstats_merge: dst_plane_stride is shorter than a plane");
+  MSFNO_REQUIRE(src_plane_stride >= N, MSFNO_EINVAL,
+                "tstats_merge: src_plane_stride is shorter than a plane");
+  return launch_tstats_merge(kind, flags, dst_count, dst_state, dst_plane_stride, src_count,
+                             src_state, src_plane_stride, N, (hipStream_t)stream);
 }
 
 // N * lmax rows of mmax complex numbers; the interleaved floats of a complex tensor sit on

@@ -232,6 +232,21 @@ int launch_pack16(const float* x, const int* slab, const PackWin& w, int S_out, 
                   hipStream_t s);
 int launch_unpack16(const unsigned short* q, const float* ref, const int* exp2, float* y,
                     int64_t n, int S, hipStream_t s);
+// ---- timestats.hip: streaming per-pixel moments over time, and their merge -----------------
+// planes of a state of this kind (MSFNO_TSTATS_FIELD / _ERROR) and flags (_MINMAX / _ANOM), 0
+// for an unknown kind or a flag the kind does not take
+int tstats_planes(int kind, int flags);
+// in0, in1 (B, S, P) with batch strides in elements (in1 null for FIELD); clim a stack of (P)
+// slabs with clim_slab (B, S) device indices, or both null; count (S, P), state (K, S, P)
+// with plane stride ps; the B updates are applied in order
+int launch_tstats_update(int kind, int flags, const float* in0, const float* in1, int64_t bs0,
+                         int64_t bs1, const float* clim, const int* clim_slab, int B, int S,
+                         int64_t P, int skip_nan, uint32_t* count, float* state, int64_t ps,
+                         hipStream_t s);
+// dst <- dst (+) src over N = S P elements
+int launch_tstats_merge(int kind, int flags, uint32_t* dcount, float* dstate, int64_t dps,
+                        const uint32_t* scount, const float* sstate, int64_t sps, int64_t N,
+                        hipStream_t s);
 // ---- regrid.hip: separable banded regridding (conservative, bilinear, block mean) ----------
 // one axis as an ELL table on the device: start and count (n_out), w (n_out, taps)
 struct RegridAxis {

@@ -15,5 +15,6 @@ from . import ensemble  # noqa: F401
 from . import filmgen  # noqa: F401
 from . import regrid  # noqa: F401
 from . import regions  # noqa: F401
+from . import timestats  # noqa: F401
 
 __version__ = "0.1.0"

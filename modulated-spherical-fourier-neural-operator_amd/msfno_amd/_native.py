@@ -233,6 +233,12 @@ SIGNATURES = [
     ("msfno_unpack16", _i, [_vp, _vp, _vp, _vp, ctypes.c_longlong, _i, _vp]),
     ("msfno_regrid", _i, [_vp, _i, _vp, _i, ctypes.POINTER(RegridAxis),
                           ctypes.POINTER(RegridAxis), _vp, _i, _f, _f, _vp, _vp]),
+    ("msfno_tstats_planes", _i, [_i, _i]),
+    ("msfno_tstats_update", _i, [_i, _i, _vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp,
+                                 _vp, _i, _i, ctypes.c_longlong, _i, _vp, _vp,
+                                 ctypes.c_longlong, _vp]),
+    ("msfno_tstats_merge", _i, [_i, _i, _vp, _vp, ctypes.c_longlong, _vp, _vp,
+                                ctypes.c_longlong, ctypes.c_longlong, _vp]),
     ("msfno_gcn_workspace_size", _sz, [_i, _i, _i, _i, _i, _i, _i]),
     ("msfno_gcn_forward", _i, [ctypes.POINTER(GcnGraph), ctypes.POINTER(GcnDesc), _vp, _vp, _i,
                                _i, _vp, _sz, _vp]),

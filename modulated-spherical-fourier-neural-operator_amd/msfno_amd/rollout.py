@@ -315,6 +315,80 @@ class Rollout:
             verifier.update(i // every, y if regrid is None else regrid(y), *item)
         return verifier.scores()
 
+    def verify_maps(self, x0, truths, steps, every=1, maps=None, normalised_input=False,
+                    regrid=None, skip_nan=False):
+        """Score maps of a rollout on the device: runs as ``verify`` does, and every scored
+        step ``i`` (``i % every == 0``) folds the batch of cases into ``maps[i // every]``,
+        an ``ErrorMaps`` of a ``timestats.LeadTimeMaps``: per-pixel bias, RMSE, MAE and ACC
+        per lead time.  Returns ``maps``; pass the same ``maps`` for the next batch of
+        initial dates.  ``truths`` are items as in ``verify``; a climatology in an item needs
+        maps built with ``anomalies=True`` (the default maps are, iff the first item has one),
+        and every slab of it is read (no -1 in a ``clim_slab``).  ``regrid`` as in ``verify``:
+        maps and truths are then of the destination grid.  With ``skip_nan`` a case is left
+        out of a pixel where its truth or climatology is NaN.
+
+        Memory: 3 planes and the count per lead time, 8 with anomalies; at 73 x 721 x 1440 a
+        plane is 303 MB and a lead time with anomalies 2.7 GB, so ``regrid=`` to 1.5 degrees
+        or a channel subset is the way to keep 40 lead times."""
+        from . import timestats as T
+        _whole_fields_only(self.model, regrid)
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.verify_maps maps whole fields; on a latitude-band rank keep a "
+                "timestats.LeadTimeMaps of the rank's own rows and update it with the rank's "
+                "rows of the output, the truth and the climatology: the maps are per pixel, "
+                "there is nothing to reduce")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        n_scored = (steps + every - 1) // every
+        B, C, H, W = x0.shape
+        if regrid is not None:
+            H, W = regrid.out_shape
+        if maps is not None:
+            if len(maps) < n_scored:
+                raise ValueError(f"maps has {len(maps)} lead times, {n_scored} needed")
+            if tuple(maps.shape) != (C, H, W):
+                raise ValueError(f"maps are of {tuple(maps.shape)} fields, the scored fields "
+                                 f"are {(C, H, W)}")
+        truths = iter(truths)
+        for i, y in self.run(x0, steps, normalised_input=normalised_input):
+            if i % every:
+                continue
+            try:
+                item = next(truths)
+            except StopIteration:
+                raise ValueError(f"truths ran out at step {i}: {n_scored} scored steps need "
+                                 "one item each") from None
+            if isinstance(item, torch.Tensor):
+                item = (item,)
+            if maps is None:
+                maps = T.LeadTimeMaps(n_scored, C, H, W, anomalies=len(item) > 1,
+                                      device=x0.device)
+            maps[i // every].update(y if regrid is None else regrid(y), *item,
+                                    skip_nan=skip_nan)
+        return maps
+
+    def statistics(self, x0, steps, stats, every=1, normalised_input=False, regrid=None):
+        """The time mean and variability of a rollout: folds every output ``i`` of
+        ``run(x0, steps)`` where ``i % every == 0`` into ``stats``, a
+        ``timestats.FieldStats`` of the output's (C, H, W) (of the destination grid under
+        ``regrid``), batch elements in order.  Returns ``stats``; pass it again to go on.
+        At 73 x 721 x 1440 a plane is 303 MB and a ``FieldStats`` is 2 planes and the count
+        (4 with ``minmax``)."""
+        _whole_fields_only(self.model, regrid)
+        if getattr(self.model, "world", 1) > 1:
+            raise NotImplementedError(
+                "Rollout.statistics folds whole fields; on a latitude-band rank keep a "
+                "timestats.FieldStats of the rank's own rows and update it with the rank's "
+                "rows of every output: the statistics are per pixel, there is nothing to "
+                "reduce")
+        if steps < 1 or every < 1:
+            raise ValueError("steps and every must be >= 1")
+        for i, y in self.run(x0, steps, normalised_input=normalised_input):
+            if i % every == 0:
+                stats.update(y if regrid is None else regrid(y))
+        return stats
+
     def verify_ensemble(self, x0, truths, steps, every=1, weights="uniform",
                         normalised_input=False, verifier=None, regrid=None):
         """Score an ensemble rollout on the device: the batch of ``x0`` (M, C, H, W) is the
